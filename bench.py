@@ -28,6 +28,10 @@ configs[1] (10k x 1 trajectory, contiguous sample shards), `--strong-config 2`: 
 samples, whole trajectories per rank, `dist.shard_by_trajectory`) -- again one all-gather per step.  Every multi-GPU line
 carries `multi_gpu`: per-rank kernel and collective times, the rank count RCCL saw, and the builder's projection.
 
+`--steps` is the number of timed steps of the headline (split into regions of about 50 steps, the median region is
+reported); `--dump-outputs DIR` writes the log-likelihoods of the last of them to DIR/logl.npy, so that two builds can
+be compared output for output on the same seeded inputs.
+
     python bench.py --gpus 1 --steps 50 --warmup 5
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
@@ -47,6 +51,9 @@ import numpy as np  # noqa: E402
 FP64_PEAK_TFLOPS = 78.6   # MI355X fp64 vector (= fp64 matrix) peak, AMD spec
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8 TB/s spec
 ROTATE = 8                # distinct batches resident in HBM, one per step in turn
+REGION_STEPS = 50         # default steps per timed region (a synchronize on both sides of every region)
+MAX_REGIONS = 60
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this much in all
 
 
 def kernel_source_hash():
@@ -173,7 +180,9 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=60, help='timed regions of exactly --steps steps; the median one is reported')
+    ap.add_argument('--repeats', type=int, default=0,
+                    help='timed regions the --steps timed steps are split into; the median region is reported '
+                         f'(0: one region per {REGION_STEPS} steps, at most {MAX_REGIONS})')
     ap.add_argument('--sustained', type=float, default=4.0, help='seconds of back-to-back steps for the `sustained` figure (0: skip)')
     ap.add_argument('--samples', type=int, default=10000, help='candidate profiles per GPU per step (weak scaling)')
     ap.add_argument('--T', type=int, default=1000)
@@ -198,7 +207,13 @@ def main():
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help="collective backend; 'gloo' (log-likelihoods staged through host memory) rehearses the "
                          "multi-rank path on a box with fewer GPUs than ranks")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the log-likelihoods of the last timed step as DIR/logl.npy (float64; a fixed, seeded sample '
+                         'of them if they exceed 64 MB)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    regions = args.repeats or min(MAX_REGIONS, max(1, args.steps // REGION_STEPS))
 
     import torch
     import torch.distributed as dist
@@ -331,22 +346,25 @@ def main():
                 d_all.copy_(bdist.all_gather_logl(d_out.cpu()))
 
     def timed(fn, steps, warmup, sample=4, handle=None, repeats=1):
-        # The timed region -- EXACTLY `steps` steps between barrier + synchronize on both sides, maximum over ranks -- is run
-        # `repeats` times and the MEDIAN region is what is reported: one region of a latency-bound launch is a millisecond
-        # long and scatters by +-5 % from run to run (round 3: 168.6 M in the driver's run, 172-178 M in the builder's).
+        # EXACTLY `steps` timed steps, split into `repeats` regions (barrier + synchronize on both sides of each, maximum over
+        # ranks per region), and the MEDIAN region's time per step is what is reported: one region of a latency-bound launch
+        # is a millisecond long and scatters by +-5 % from run to run (round 3: 168.6 M in the driver's run, 172-178 M in the
+        # builder's).  Returned: that time per step times `steps`, as callers divide by `steps`.
         # (kernel durations from HIP events around every `sample`-th launch of the timed regions: the events cost a few
         # microseconds per launch, which every step would otherwise pay)
+        repeats = max(1, min(repeats, steps))
+        region_sizes = [len(r) for r in np.array_split(np.arange(steps), repeats)]
         for _ in range(warmup):
             fn()
         coll_events.clear()
         _lib.kernel_timing(sample if steps >= 2 * sample else 1)
         dts = []
-        for _ in range(repeats):
+        for size in region_sizes:
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for _ in range(steps):
+            for _ in range(size):
                 fn()
             torch.cuda.synchronize()
             if world > 1:
@@ -358,18 +376,19 @@ def main():
         timed.frames_per_launch = _lib.frames_run_read(handle or h) / max(launches, 1)   # counted on the device by the tasks themselves
         timed.walk_ms = wms / max(wl, 1)
         dts = np.array(dts)
-        timed.local_dt = float(np.median(dts))
+        timed.local_dt = float(np.median(dts / region_sizes)) * steps
         if world > 1:
             t = torch.from_numpy(dts).to(dev if args.backend == 'nccl' else 'cpu')
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dts = t.cpu().numpy()
-        q25, med, q75 = (float(v) for v in np.percentile(dts, [25, 50, 75]))
-        per = 1e3 / steps
-        timed.stats = {'repeats': int(repeats), 'median': med * per, 'q25': q25 * per, 'q75': q75 * per, 'iqr': (q75 - q25) * per,
-                       'min': float(dts.min()) * per, 'max': float(dts.max()) * per, 'timed_region_s': float(dts.sum()),
-                       'what': f'ms per step over {repeats} timed regions of exactly {steps} steps each (barrier + synchronize on both '
-                               'sides, maximum over ranks per region); `value` and `ms_per_step` are the median region'}
-        return med, kms / max(launches, 1), kname
+        per_step = dts / region_sizes * 1e3
+        q25, med, q75 = (float(v) for v in np.percentile(per_step, [25, 50, 75]))
+        timed.stats = {'repeats': int(repeats), 'median': med, 'q25': q25, 'q75': q75, 'iqr': q75 - q25,
+                       'min': float(per_step.min()), 'max': float(per_step.max()), 'timed_region_s': float(dts.sum()),
+                       'what': f'ms per step over {repeats} timed regions of {min(region_sizes)}-{max(region_sizes)} steps, {steps} steps in all '
+                               '(barrier + synchronize on both sides, maximum over ranks per region); `value` and `ms_per_step` '
+                               'are the median region'}
+        return med * 1e-3 * steps, kms / max(launches, 1), kname
 
     def sustained(fn, seconds, per_step_s, chunk=512):
         """
@@ -390,7 +409,19 @@ def main():
         wall = time.perf_counter() - t0
         return chunks * chunk / wall, wall
 
-    dt, kernel_ms, kname = timed(step, args.steps, args.warmup, repeats=args.repeats)
+    dt, kernel_ms, kname = timed(step, args.steps, args.warmup, repeats=regions)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: this rank's log-likelihoods, or every rank's after the all-gather
+        if world > 1:
+            last = d_all.view(world, pad).cpu().numpy()
+            last = np.concatenate([last[r, :sizes[r]] for r in range(world)])
+        else:
+            last = d_out[:n].cpu().numpy()
+        cap = (DUMP_BYTES - 4096) // last.itemsize
+        if last.size > cap:
+            last = last[np.sort(np.random.default_rng(0).choice(last.size, cap, replace=False))]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'logl.npy'), np.ascontiguousarray(last, dtype=np.float64))
     walk_ms = timed.walk_ms
     headline_stats = timed.stats
     value = n_global * args.steps / dt
@@ -518,7 +549,7 @@ def main():
             sturn[0] += 1
             return sampler.logL(ss_, th_)
         got = sampler.logL(*seam_batches[0])
-        sdt, skms, _ = timed(seam_step, args.steps, min(args.warmup, 3), repeats=args.repeats)
+        sdt, skms, _ = timed(seam_step, args.steps, min(args.warmup, 3), repeats=regions)
         result['api_seam'] = {
             'what': 'FixedkSampler.logL(ss, thetas): host (N,k+1) float64 + int64 in, host (N,) float64 out, per step '
                     '(bild/amis.py:717-739); the rows go up as they are (float64 + one byte per state) and are converted on the device',
