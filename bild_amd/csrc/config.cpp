@@ -50,7 +50,6 @@ void load(Config &c)
     num("BILD_PAIRS_MAX_GAP", c.pairs_max_gap);
     if (c.pairs_max_gap < 2) c.pairs_max_gap = 2;
     num("BILD_PAIRS_MAX_TASKS", c.pairs_max_tasks);
-    num("BILD_TABLES_AFTER", c.tables_after);
     flag("BILD_NO_JUMP", c.no_jump);
     flag("BILD_NO_SPLIT", c.no_split);
     flag("BILD_NO_WALK_PLAN", c.no_walk_plan);
@@ -59,13 +58,8 @@ void load(Config &c)
     flag("BILD_DENSE_VALU", c.dense_valu);
     flag("BILD_NO_FUSED_LAUNCH", c.no_fused_launch);
     num("BILD_GEOM", c.geom);
-    num("BILD_WORK_BLOCKS", c.work_blocks);
     num("BILD_WIDE_THREADS", c.wide_threads);
     num("BILD_WALK_DEBUG", c.walk_debug);
-    if (const char *e = getenv("BILD_SCHED_MODE")) {
-        c.sched_mode = e;
-        note("BILD_SCHED_MODE", e);
-    }
     flag("BILD_IN_VIA_COPY", c.in_via_copy);
     flag("BILD_OUT_VIA_COPY", c.out_via_copy);
     flag("BILD_ST_ON_HOST", c.st_on_host);

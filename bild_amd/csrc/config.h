@@ -23,7 +23,6 @@ struct Config {
     int states_stride = 3;                        // BILD_STATES_STRIDE     the state table keeps every n-th gap (1 ... 8)
     int pairs_max_gap = 128;                      // BILD_PAIRS_MAX_GAP
     int64_t pairs_max_tasks = (int64_t)40 << 20;  // BILD_PAIRS_MAX_TASKS
-    int64_t tables_after = -1;                    // BILD_TABLES_AFTER     experiments: delay the tables (-1: the built-in thresholds)
     // launches
     bool no_jump = false;            // BILD_NO_JUMP            frame by frame behind the first switch
     bool no_split = false;           // BILD_NO_SPLIT           single launch
@@ -33,10 +32,8 @@ struct Config {
     bool dense_valu = false;         // BILD_DENSE_VALU         dense path on the vector pipe
     bool no_fused_launch = false;    // BILD_NO_FUSED_LAUNCH    walk and frame loop as two launches (A/B against the fused grid)
     int geom = -1;                   // BILD_GEOM               force a geometry id
-    int work_blocks = 0;             // BILD_WORK_BLOCKS
     int wide_threads = 0;            // BILD_WIDE_THREADS       256 / 512 / 1024
     int walk_debug = 0;              // BILD_WALK_DEBUG
-    std::string sched_mode;          // BILD_SCHED_MODE         "spread" / "sorted"
     // the host-buffer seam
     bool in_via_copy = false;  // BILD_IN_VIA_COPY
     bool out_via_copy = false; // BILD_OUT_VIA_COPY

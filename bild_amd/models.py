@@ -208,7 +208,7 @@ class MultiStateRouse(MultiStateModel):
         prints, arrs = self._fingerprints(items)
         if expect is not None and expect < 0:
             raise ValueError("expect must be a non-negative number of evaluations")
-        # (api.cpp: kExpectPrefix, kExpectPairs, and the budget of the transient state table: 64 instead of 4 GB from 1e8 on)
+        # (tables.cpp: kExpectPrefix, kExpectPairs, and the budget of the transient state table: 64 instead of 4 GB from 1e8 on)
         table_class = 2 if expect is None else (3 if expect >= 10 ** 8 else 2 if expect >= 3000 else 1 if expect >= 300 else 0)
         key = (table_class,) + tuple(id(t) if p[0] is not None else p for t, p in zip(items, prints))
         hit = self._trajsets.get(key)

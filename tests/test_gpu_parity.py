@@ -633,7 +633,7 @@ def test_baseline_config4_full_samples_per_trajectory(built_lib):
         alone = model.logL_segments(seg_start[sl][::-1], seg_state[sl][::-1], trajs, tid[sl][::-1])[::-1]
         assert np.array_equal(alone, results['auto'][sl])
     # one trajectory at a time through the sampler seam: a trajectory set of its own.  Whether a set gets the pair table
-    # (api.cpp: ensure_pairs) depends on its size; where two sets differ in that, the pieces of a sum are cut differently and
+    # (tables.cpp: ensure_pairs) depends on its size; where two sets differ in that, the pieces of a sum are cut differently and
     # the values agree to rounding (1e-11 observed), not to the bit -- the bar here covers both cases
     for j in (1, 5):
         sl = slice(j * per, (j + 1) * per)
@@ -951,7 +951,7 @@ def test_prefix_table_and_launch_order_do_not_change_results(built_lib, case):
 def test_launch_order_of_a_throughput_bound_batch(built_lib):
     """
     Batches of several rounds with more busy candidates than one round has waves get the sorted launch order (candidates of
-    equal work share a wave), smaller ones the spread order (api.cpp: schedule).  Either way a permutation, and never a
+    equal work share a wave), smaller ones the spread order (launch.cpp: schedule).  Either way a permutation, and never a
     different result: 30 000 candidates with six switches each on a short trajectory, against the same batch in array order.
     """
     import torch
@@ -988,7 +988,7 @@ def test_launch_order_of_a_throughput_bound_batch(built_lib):
 @pytest.mark.parametrize('S', [2, 3])
 def test_pair_table_two_close_switches_run_no_frame(built_lib, S):
     """
-    Second-level transient table (csrc/common.h "pair table", api.cpp ensure_pairs): two switches closer together than the
+    Second-level transient table (csrc/common.h "pair table", tables.cpp ensure_pairs): two switches closer together than the
     first one's transient come out of ONE entry, keyed by (old, middle, new state, frame, gap).  Designed candidates:
     pairs at every kind of place (frame 1, mid-trajectory, the second switch on the last frame / beyond the end), gaps
     from 1 up to beyond the table's range, followed by nothing, by a far third switch, or by a near one (a chain of

@@ -16,6 +16,13 @@ VDIR = os.path.join(ROOT, 'bild_amd', 'variants')
 CSRC = os.path.join(ROOT, 'bild_amd', 'csrc')
 
 
+def sources():
+    # every translation unit of the library (bild_amd/csrc/Makefile: HOST_SRCS, HIP_SRCS); asan_stubs.cpp stands in for the
+    # device code in the host-only sanitizer build
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))
+            if (f.endswith('.cpp') or f.endswith('.hip')) and f != 'asan_stubs.cpp']
+
+
 def build(specs):
     os.makedirs(VDIR, exist_ok=True)
     for f in os.listdir(VDIR):
@@ -24,9 +31,7 @@ def build(specs):
     for spec in specs:
         name, _, flags = spec.partition(':')
         out = os.path.join(VDIR, f'libbild_amd_{name}.so')
-        cmd = ['hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-shared'] + flags.split() + \
-              [os.path.join(CSRC, f) for f in ('api.cpp', 'amis_host.cpp', 'comm.cpp', 'kernels.hip', 'walk.hip', 'wide.hip', 'dense_mfma.hip',
-                                               'modal_mfma.hip', 'amis_device.hip', 'schedule.hip')] + ['-o', out]
+        cmd = ['hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-shared'] + flags.split() + sources() + ['-o', out]
         procs.append((name, subprocess.Popen(cmd)))
     for name, p in procs:
         if p.wait() != 0:
