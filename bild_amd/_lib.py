@@ -26,7 +26,7 @@ NO_SPLIT = 0x80
 NO_STATES = 0x100
 NO_TAIL = 0x200
 
-Q_N, Q_D, Q_S, Q_MODAL_OK, Q_NP, Q_NEFF, Q_HAS_G = range(7)
+Q_N, Q_D, Q_S, Q_MODAL_OK, Q_NP, Q_NEFF, Q_HAS_G, Q_LAST_GEOMETRY = range(8)
 X_LAMBDA, X_SIGMA, X_Q, X_WQ, X_R, X_C0Q, X_V = range(7)
 
 

@@ -14,7 +14,7 @@ int padded_rows(int n)
         if (r >= n) return r;
     return 0;
 }
-bool geometry_for(int, int, int64_t, int, Geometry *) { return false; }
+bool geometry_for(int, int, int64_t, int, Geometry *, bool, bool) { return false; }
 const char *kernel_name(const Geometry &, int) { return "none"; }
 int launch_logl(const Geometry &, int, const KParams &, int, size_t, void *, void *, void *) { return 1; }
 int launch_reduce_partials(const double *, double *, int64_t, int, void *) { return 1; }

@@ -193,6 +193,7 @@ struct Geometry {
     int OCC;        // wavefronts per SIMD the register allocation is bounded for
     int id;         // index into the compiled-kernel table
     int modes;      // paths that may pick it automatically: 1 dense, 2 modal; 0: only through BILD_GEOM
+    int lay;        // layout (BILD_GEOMETRIES): 0 packed, 1 block, 2 row, 3 / 4 row / packed of the listed frame loop
     int tasks_per_wave() const { return 64 / G; }
     // mean vectors a group can carry next to the NP covariance columns (a covariance chain needs one per
     // dimension that shares its localization error: d for d* = 1, fewer when the errors differ)
@@ -224,8 +225,9 @@ int launch_validate(const int32_t *seg_start, const int32_t *seg_state, const in
 int padded_rows(int n_rows);
 // launch geometry for `ntasks` recursions of a chain padded to NP rows, each with up to `means` mean vectors
 // (several are compiled per NP: few tasks per wave for small batches, many for throughput, fewer lanes per
-// task when fewer mean vectors are needed); env BILD_GEOM=<id> overrides.
-bool geometry_for(int NP, int mode, int64_t ntasks, int means, Geometry *g);
+// task when fewer mean vectors are needed); env BILD_GEOM=<id> overrides where it fits (`forced` = false: never -- the
+// launches that build a table; the rule is written at the definition); `jumps`: the launch may jump (no block layout).
+bool geometry_for(int NP, int mode, int64_t ntasks, int means, Geometry *g, bool forced = true, bool jumps = false);
 const char *kernel_name(const Geometry &g, int mode);
 // the geometry of the frame loop over the work lists of a split launch, where it differs from `from` (same layout, same
 // arithmetic, another register budget); false: keep `from`

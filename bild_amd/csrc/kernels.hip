@@ -258,6 +258,7 @@ __device__ __forceinline__ void logl_body(const KParams &p)
     // the frame loop over the work lists ONLY (geometries 23 / 24 / 25): never builds a table, so the instantiation carries none
     // of the builders' tests in its frame loop, and has a frame loop of its own (below)
     constexpr bool kLean = LAY == 3 || LAY == 4; // (4: the packed layout, likewise for the listed launch only)
+    static_assert(!(BLK && JUMP), "the block layout runs frame by frame only (see BILD_GEOMETRIES)");
     static_assert(LAY == 0 || LAY == 4 || (G == 16 && CPL == 1), "block / row layouts: 16 lanes per task, one column per lane");
     constexpr int MS = table_stride(NP); // LDS matrix stride
     constexpr int SB = StateBlock::size(NP);
@@ -851,28 +852,21 @@ __device__ __forceinline__ void logl_body(const KParams &p)
         if (BLK) group_mask = 0x000F000F000F000Full << (4 * grp);
         else group_mask = (G == 64 ? ~0ull : ((1ull << G) - 1)) << (grp * G);
         // log-likelihood of the frames behind the accumulators (pyx:88, 251-256), the same in every lane of the task
-        auto piece_value = [&]() {
-            double acc = 0.0;
+        // sum over the task's mean columns of one value per column, in column order (the same in every lane of the task).  The
+        // order must not depend on how columns are dealt to lanes: a lane of a three-column geometry holds two mean columns, and
+        // adding those on the lane first made geometry 11 differ from geometry 10 in the last bits at NP = 20.
+        auto mean_sum = [&](const double (&v)[CPL]) {
 #pragma unroll
-            for (int q = 0; q < CPL; ++q) acc += isM[q] ? accq[q] : 0.0;
-            scratch[gl] = acc;
+            for (int q = 0; q < CPL; ++q)
+                if (!isC[q] && hasImg[q]) scratch[cidx[q]] = isM[q] ? v[q] : 0.0;
             wave_lds_fence();
             double tot = 0.0;
 #pragma unroll
-            for (int g2 = 0; g2 < G; ++g2) tot += scratch[g2];
-            wave_lds_fence();
-            return piece_from_sums(tot, P, E, nv, nd);
-        };
-        // sum of one value per lane over the lanes of the task, in lane order (the same in every lane of the task)
-        auto group_sum = [&](double v) {
-            scratch[gl] = v;
-            wave_lds_fence();
-            double tot = 0.0;
-#pragma unroll
-            for (int g2 = 0; g2 < G; ++g2) tot += scratch[g2];
+            for (int m = 0; m < MC; ++m) tot += scratch[NP + m];
             wave_lds_fence();
             return tot;
         };
+        auto piece_value = [&]() { return piece_from_sums(mean_sum(accq), P, E, nv, nd); };
         auto reset_piece = [&]() {
 #pragma unroll
             for (int q = 0; q < CPL; ++q) accq[q] = 0.0;
@@ -1192,18 +1186,20 @@ __device__ __forceinline__ void logl_body(const KParams &p)
                     }
                     if (far) {
                         converged = true;
-                        double mine = 0.0;
+                        double mine[CPL];
 #pragma unroll
-                        for (int q = 0; q < CPL; ++q)
+                        for (int q = 0; q < CPL; ++q) {
+                            mine[q] = 0.0;
                             if (isM[q]) {
                                 const double *__restrict__ gq =
                                     p.tail_g + ((td->prefix_rec0 + ((int64_t)e * S + s) * T + (t - 1)) * kDMax + (cidx[q] - NP)) * NP;
                                 double acc = 0.0;
 #pragma unroll
                                 for (int i = 0; i < NP; ++i) acc = fma(gq[i], col.v[q][i] - rec[cidx[q] * NP + i], acc);
-                                mine += acc;
+                                mine[q] = acc;
                             }
-                        tail_term = group_sum(mine);
+                        }
+                        tail_term = mean_sum(mine);
                     }
                 }
             }
@@ -1450,8 +1446,9 @@ int launch_geom(int mode, const KParams &p, int grid, size_t lds, hipStream_t st
         }
     }
     if (p.trans_dump || p.trans2_dump) {
-        // the transient / pair / state tables: the BUILD instantiation of the geometry (never the lean ones, see above)
-        if constexpr (LAY <= 2) {
+        // the transient / pair / state tables: the BUILD instantiation of the geometry (never the lean ones, see above, nor the
+        // block layout, which does not jump)
+        if constexpr (LAY == 0 || LAY == 2) {
             if (mode != kModal || !p.prefix || p.no_jump) return (int)hipErrorInvalidValue;
             if (flavor == 0) return go(logl_kernel<NP, CPL, G, W, OCC, LAY, kModal, 0, false, true, true>);
             if (flavor == 1) return go(logl_kernel<NP, CPL, G, W, OCC, LAY, kModal, 1, false, true, true>);
@@ -1461,9 +1458,13 @@ int launch_geom(int mode, const KParams &p, int grid, size_t lds, hipStream_t st
         }
     }
     if (mode == kModal && p.prefix && !p.no_jump) {
-        if (flavor == 0) return go(logl_kernel<NP, CPL, G, W, OCC, LAY, kModal, 0, false, true>);
-        if (flavor == 1) return go(logl_kernel<NP, CPL, G, W, OCC, LAY, kModal, 1, false, true>);
-        return go(logl_kernel<NP, CPL, G, W, OCC, LAY, kModal, 2, false, true>);
+        if constexpr (LAY == 1) {
+            return (int)hipErrorInvalidValue; // (the block layout runs frame by frame only: see BILD_GEOMETRIES)
+        } else {
+            if (flavor == 0) return go(logl_kernel<NP, CPL, G, W, OCC, LAY, kModal, 0, false, true>);
+            if (flavor == 1) return go(logl_kernel<NP, CPL, G, W, OCC, LAY, kModal, 1, false, true>);
+            return go(logl_kernel<NP, CPL, G, W, OCC, LAY, kModal, 2, false, true>);
+        }
     }
     if (mode == kModal) {
         if (flavor == 0) return go(logl_kernel<NP, CPL, G, W, OCC, LAY, kModal, 0>);
@@ -1498,7 +1499,10 @@ int launch_geom(int mode, const KParams &p, int grid, size_t lds, hipStream_t st
 //    faster than the packed (1, 13) / (1, 15) at every batch size, 7 % with missing frames: the f64 matrix
 //    and vector pipes share their FMA throughput, so only the redundancy of the per-lane S chain is saved.
 //    Not selected automatically: its S is summed in another order, and with it the results of one profile
-//    would differ in the last bits between batch sizes (all other geometries of an NP agree bit for bit).
+//    would differ in the last bits between batch sizes (all other geometries of an NP agree bit for bit).  Frame by frame
+//    only: its jumping instantiation is neither compiled nor dispatched (launch_geom, geometry_for).  Forced onto split launches
+//    it returned NaN for some rows; the cause is not known -- not the block sum (the f64 MFMA sums each 16-lane block
+//    correctly under a partial EXEC mask, measured on MI355X), and the other layouts pass the same launches bit for bit.
 //  * NP = 10 / 12, one column per lane, G = 16, row layout (ids 21 / 22): a task is one 16-lane row and every use of
 //    (C w)_i reads lane i of the row by DPP row broadcast inside the FMA itself (v_fmac_f64_dpp ... row_newbcast) --
 //    no LDS all-gather in the frame loop, 20 registers less.  Same operations in the same order as the packed
@@ -1547,7 +1551,7 @@ int launch_geom(int mode, const KParams &p, int grid, size_t lds, hipStream_t st
     X(16, 12, 1, 16, 4, 2, 1, 0)
 
 constexpr Geometry kGeoms[] = {
-#define X(ID, NP, CPL, G, W, OCC, LAY, MODES) {NP, CPL, G, W, OCC, ID, MODES},
+#define X(ID, NP, CPL, G, W, OCC, LAY, MODES) {NP, CPL, G, W, OCC, ID, MODES, LAY},
     BILD_GEOMETRIES(X)
 #undef X
 };
@@ -1561,12 +1565,22 @@ int padded_rows(int n_rows)
     return 0;
 }
 
-bool geometry_for(int NP, int mode, int64_t ntasks, int means, Geometry *g)
+// BILD_GEOM=<id> (diagnostics and tests) forces geometry `id` onto every evaluating launch of the vector kernels that it fits:
+// the same padded row count, room for `means` mean vectors, and a path its last field admits -- where that field is 0 (the
+// geometries never picked automatically: the block layouts 15 / 16, the lean frame loops 23 / 24 / 25, all of them modal
+// layouts) it counts as modal.  A launch it does not fit takes the automatic choice below (BILD_Q_LAST_GEOMETRY tells which
+// geometry ran): the dense instantiations of the modal-only geometries are compiled, launch_geom being generic, but never run.
+// Launches that BUILD a table never take the forced geometry (`forced` = false: the transient and pair tables, whose builder
+// launches go through launch_batch; the prefix table takes builder_geometry): the lean geometries cannot build one, and the
+// tables of a set, with all the results read out of them, do not depend on the switch.
+// A launch that may jump (`jumps`) never takes the block layout (LAY 1): see BILD_GEOMETRIES.
+bool geometry_for(int NP, int mode, int64_t ntasks, int means, Geometry *g, bool forced, bool jumps)
 {
-    if (bild::config().geom >= 0) {
+    if (forced && bild::config().geom >= 0) {
         const int id = bild::config().geom;
+        const int path = mode == kDense ? 1 : 2;
         for (const Geometry &c : kGeoms)
-            if (c.id == id && c.NP == NP && c.mean_slots() >= means) {
+            if (c.id == id && c.NP == NP && c.mean_slots() >= means && ((c.modes ? c.modes : 2) & path) && !(jumps && c.lay == 1)) {
                 *g = c;
                 return true;
             }

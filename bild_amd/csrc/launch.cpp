@@ -97,8 +97,14 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
         // (the frame loop over the work lists is latency-bound: the row layout -- three mean slots, the shortest frame for a lone
         // wave -- also where fewer mean vectors would allow more tasks per wave; all geometries of a chain length agree bit for bit)
         const int means_for_geometry = may_split ? std::max(ts.means_max, (int)kDMax) : ts.means_max;
-        if (!geometry_for(m.NPm[mode], mode, tasks_for_geometry, means_for_geometry, &geom) &&
-            !geometry_for(m.NPm[mode], mode, tasks_for_geometry, ts.means_max, &geom))
+        // (a launch that builds a table takes the automatic geometry whatever BILD_GEOM says, a launch that may jump never the
+        // block layout: see geometry_for; a forced geometry is held to the mean vectors the set needs, not to the three slots a
+        // split launch prefers)
+        const bool forced = !building && config().geom >= 0;
+        const bool jumps = mode == kModal && K1 > 0 && !(flags & (BILD_NO_PREFIX | BILD_NO_JUMP)) && !config().no_prefix && !config().no_jump;
+        if (!(forced && geometry_for(m.NPm[mode], mode, tasks_for_geometry, ts.means_max, &geom, true, jumps) && geom.id == config().geom) &&
+            !geometry_for(m.NPm[mode], mode, tasks_for_geometry, means_for_geometry, &geom, !building, jumps) &&
+            !geometry_for(m.NPm[mode], mode, tasks_for_geometry, ts.means_max, &geom, !building, jumps))
             return fail(BILD_ERR_UNSUPPORTED, "no kernel for %d rows", m.NPm[mode]);
         Geometry lg{};
         // (... including the room for the walk plan in the workgroup's share of the LDS)
@@ -341,6 +347,7 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
               : fam == kDenseTiles ? launch_logl_dense_mfma(m.NPm[kDense], p, (void *)st)
                                    : launch_logl(geom, mode, p, grid, lds, (void *)st, timing ? (void *)own.e0 : nullptr, timing ? (void *)own.e1 : nullptr);
     if (lrc != 0) return fail(BILD_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
+    if (!building) m.last_geom = fam == kVector && frame_loop ? geom.id : -1;
     if (timing) {
         if (!frame_loop) HIP_TRY(hipEventRecord(own.e0, st)); // (no dispatch for the events to ride on: an empty bracket)
         if (!ride || !frame_loop) HIP_TRY(hipEventRecord(own.e1, st));

@@ -139,6 +139,9 @@ struct bild_model {
         return slots[1].stream == st ? &slots[1] : nullptr;
     }
     mutable PinnedBuf h_status; // (s, theta) rows refused on the device by calls nobody waited for: sticky until bild_logl_st_status
+    // id of the vector geometry whose frame loop the last evaluating launch ran (BILD_Q_LAST_GEOMETRY); -1: another kernel family,
+    // or a split launch whose table walk finished the batch.  Table builders leave it alone.
+    mutable std::atomic<int> last_geom{-1};
 };
 
 struct bild_trajset {

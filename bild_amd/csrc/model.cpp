@@ -467,6 +467,7 @@ int bild_model_query(const bild_model *m, int what, int64_t *value)
     case BILD_Q_NP: *value = m->NP; break;
     case BILD_Q_NEFF: *value = m->n; break;
     case BILD_Q_HAS_G: *value = m->has_G; break;
+    case BILD_Q_LAST_GEOMETRY: *value = m->last_geom; break;
     default: return fail(BILD_ERR_INVALID, "unknown query %d", what);
     }
     return BILD_OK;

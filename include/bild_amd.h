@@ -140,6 +140,10 @@ int bild_model_destroy(bild_model *m);
 #define BILD_Q_NP           4 /* padded row count the kernels run with                    */
 #define BILD_Q_NEFF         5 /* modes kept after invariant-subspace reduction            */
 #define BILD_Q_HAS_G        6 /* 1 if any G entry is non-zero                             */
+#define BILD_Q_LAST_GEOMETRY 7 /* id of the vector-kernel geometry (BILD_GEOMETRIES) whose
+                                  frame loop ran the last evaluating launch on this model;
+                                  -1: another kernel family, a split launch whose table
+                                  walk finished the batch (no frame loop), or none yet      */
 int bild_model_query(const bild_model *m, int what, int64_t *value);
 
 /* Host-analysis export (for tests that run without a GPU).  `what`:
