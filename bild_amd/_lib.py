@@ -130,6 +130,14 @@ _SIGNATURES = {
     'bild_run_sampler_data': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _vp, _dp]),
     'bild_run_take_core': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     'bild_run_totals': (ctypes.c_int, [_vp, _vp]),
+    # GenericGaussianModel (gauss.cpp)
+    'bild_gauss_model_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _ip, _dp, _dp, _dp, ctypes.POINTER(_vp)]),
+    'bild_gauss_model_destroy': (ctypes.c_int, [_vp]),
+    'bild_gauss_trajset_create': (ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, ctypes.POINTER(_vp)]),
+    'bild_gauss_trajset_destroy': (ctypes.c_int, [_vp]),
+    'bild_gauss_trajset_info': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
+    'bild_gauss_logl_segments': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, _dp]),
+    'bild_gauss_logl_st': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _dp, _vp, _ip, _dp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -298,6 +306,75 @@ class TrajSetHandle:
         if getattr(self, '_h', None) and _lib is not None:
             _lib.bild_trajset_destroy(self._h)
             self._h = None
+
+
+class GaussModelHandle:
+    """ owns a ``bild_gauss_model*`` (GenericGaussianModel: host memory only) """
+
+    def __init__(self, order, mean, msd, msd_inf):
+        order, mean, msd, msd_inf = i32(order), f64(mean), f64(msd), f64(msd_inf)
+        S, d, L1 = msd.shape
+        assert order.shape == (S, d) and mean.shape == (S, d) and msd_inf.shape == (S, d)
+        self.S, self.d, self.Tmax = S, d, L1 - 1
+        self._h = _vp()
+        check(lib().bild_gauss_model_create(S, d, L1 - 1, iptr(order), dptr(mean), dptr(msd), dptr(msd_inf), ctypes.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, '_h', None) and _lib is not None:
+            _lib.bild_gauss_model_destroy(self._h)
+            self._h = None
+
+
+class GaussTrajSetHandle:
+    """ owns a ``bild_gauss_trajset*``: the trajectories and their interval tables on the device """
+
+    def __init__(self, model, trajs):
+        self.model = model  # keep alive
+        arrs = [f64(t) for t in trajs]
+        for a in arrs:
+            if a.ndim != 2 or a.shape[1] != model.d:
+                raise AssertionError(f"trajectory shape {a.shape} does not match model dimension d={model.d}")
+        self.T = i32([a.shape[0] for a in arrs])
+        x = f64(np.concatenate(arrs, axis=0))
+        self.n_traj = len(arrs)
+        self._h = _vp()
+        check(lib().bild_gauss_trajset_create(model._h, self.n_traj, iptr(self.T), dptr(x), ctypes.byref(self._h)))
+
+    def info(self):
+        """ (table bytes, build ms) """
+        b, ms = ctypes.c_int64(0), ctypes.c_double(0)
+        check(lib().bild_gauss_trajset_info(self._h, ctypes.byref(b), ctypes.byref(ms)))
+        return b.value, ms.value
+
+    def __del__(self):
+        if getattr(self, '_h', None) and _lib is not None:
+            _lib.bild_gauss_trajset_destroy(self._h)
+            self._h = None
+
+
+def gauss_logl_segments(model, ts, seg_start, seg_state, traj_id=None):
+    seg_start, seg_state = i32(seg_start), i32(seg_state)
+    n, K1 = seg_start.shape
+    assert seg_state.shape == (n, K1)
+    tid = None if traj_id is None else i32(traj_id)
+    assert tid is None or tid.shape == (n,)
+    out = np.empty(n, dtype=np.float64)
+    check(lib().bild_gauss_logl_segments(model._h, ts._h, n, K1, iptr(seg_start), iptr(seg_state), iptr(tid), dptr(out)))
+    return out
+
+
+def gauss_logl_st(model, ts, ss, thetas, traj_id=None):
+    ss = f64(ss)
+    thetas = np.ascontiguousarray(thetas, dtype=np.int64)
+    if ss.ndim == 1:
+        ss, thetas = ss[None, :], thetas[None, :]
+    n, K1 = thetas.shape
+    assert ss.shape == (n, K1)
+    tid = None if traj_id is None else i32(traj_id)
+    assert tid is None or tid.shape == (n,)
+    out = np.empty(n, dtype=np.float64)
+    check(lib().bild_gauss_logl_st(model._h, ts._h, n, K1, dptr(ss), aptr(thetas), iptr(tid), dptr(out)))
+    return out
 
 
 def logl_segments(model, ts, seg_start, seg_state, traj_id=None, path='auto', prefix=True, jump=True, split=True, states=True, tail=True):

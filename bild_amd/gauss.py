@@ -1,0 +1,263 @@
+"""
+`GenericGaussianModel`: the reference's model-agnostic Gaussian model (bild/models.py:536-728), with its likelihood
+evaluated on the GPU from per-trajectory interval tables (include/bild_amd.h, "GenericGaussianModel").
+
+Every pure state is a Gaussian process given by its MSD, its mean and its steady-state order, per dimension; a profile's
+likelihood is the product over its intervals of the Gaussian densities of the interval's frames, conditioned on the last
+frame before the interval (ss_order 0) or built from the increments (ss_order 1).  The covariance rule that turns an MSD
+into a covariance (the reference's ``bayesmsd.gp.msd2C_fun``) is `covariance` below.
+"""
+from collections import OrderedDict
+
+import numpy as np
+
+from . import _lib
+from .models import MultiStateModel, MultiStateRouse
+from .profiles import segments_from_states
+from .trajectory import Trajectory
+
+MAX_T = 2048    # longest trajectory the GPU tables accept (gauss.h: kGaussMaxT)
+
+
+def covariance(msd, msd_inf, ti, ss_order):
+    """
+    Covariance of a process observed at the integer times ``ti`` (ascending), from its MSD at integer lags (``msd[lag]``):
+
+    * ss_order 0, the positions:  ``C_ij = (msd_inf - msd(|ti_i - ti_j|)) / 2``;
+    * ss_order 1, the increments between consecutive times:
+      ``K_ij = (msd(ti_{i+1} - ti_j) + msd(ti_i - ti_{j+1}) - msd(ti_{i+1} - ti_{j+1}) - msd(ti_i - ti_j)) / 2``, lags taken
+      in absolute value.
+
+    This is the rule of ``bayesmsd.gp.msd2C_fun`` as its documentation defines it.
+    """
+    msd = np.asarray(msd, dtype=np.float64)
+    ti = np.asarray(ti, dtype=np.int64)
+    if ss_order == 0:
+        return 0.5 * (msd_inf - msd[np.abs(ti[:, None] - ti[None, :])])
+    if ss_order == 1:
+        a, b = ti[:-1], ti[1:]
+        lag = lambda x, y: msd[np.abs(x[:, None] - y[None, :])]
+        return 0.5 * (lag(b, a) + lag(a, b) - lag(b, b) - lag(a, a))
+    raise ValueError(f"ss_order should be in {{0, 1}}; was {ss_order}")
+
+
+def _tabulate(fun, ss_order, n_lags):
+    """ a callable MSD at the lags 0 .. n_lags - 1 and (ss_order 0) at infinity """
+    lags = np.arange(n_lags, dtype=np.float64)
+    with np.errstate(all='ignore'):
+        try:
+            vals = np.asarray(fun(lags), dtype=np.float64)
+        except Exception:
+            vals = None
+        if vals is None or vals.shape != lags.shape:
+            vals = np.array([float(fun(t)) for t in lags])
+        inf = float(fun(np.inf)) if ss_order == 0 else 0.0
+    return vals, inf
+
+
+class GenericGaussianModel(MultiStateModel):
+    """
+    Pure states are Gaussian processes; correlations between them are minimal (reference bild/models.py:536-728).
+
+    The model needs no physics: only the MSD of each pure state, for example from control experiments.  Within an
+    interval the trajectory follows its state's process; across a switch only continuity is kept: an ss_order-0 state
+    conditions on the last valid point before the interval, an ss_order-1 state starts its increments there.
+
+    Parameters
+    ----------
+    state_spec : (nStates, d, 3) nested sequence of ``(msd, m, ss_order)``
+        ``msd`` is a callable MSD function (evaluated once, on an array of the lags 0 .. 2047 and, for ss_order 0, at
+        ``np.inf``) or an array of its values: the lags 0, 1, ... and, for ss_order 0, msd(inf) as the last entry.  ``m``
+        is the mean (of the positions for ss_order 0, of the increments for ss_order 1), ``ss_order`` is 0 or 1.
+
+    Notes
+    -----
+    * The likelihood runs on the GPU: a trajectory set builds one table of every window's term per state (see
+      include/bild_amd.h), after which an evaluation is k + 1 lookups.  Trajectories are limited to 2048 frames, and to
+      the lags the MSD arrays cover.
+    * Where the reference conditions a later ss_order-0 interval on a window without any valid frame it raises
+      IndexError; here that candidate's logL is NaN, so that a batch does not fail as a whole.
+    * The reference's ``MSD_function_powerlaw`` and ``MSD_function_twoLocusRouse`` helpers are not provided: they build
+      on ``bayesmsd.deco.imaging``, which is not available to this package.  Any callable or array of MSD values works.
+    * ``initial_loopingprofile`` raises NotImplementedError, as in the reference.
+    """
+
+    def __init__(self, state_spec):
+        spec = [[tuple(entry) for entry in state] for state in state_spec]
+        if len(spec) == 0 or any(len(state) != len(spec[0]) for state in spec) or len(spec[0]) == 0 \
+                or any(len(entry) != 3 for state in spec for entry in state):
+            raise ValueError("state_spec must have shape (nStates, d, 3): (msd, m, ss_order) per state and dimension")
+        S, d = len(spec), len(spec[0])
+        order = np.zeros((S, d), dtype=np.int32)
+        mean = np.zeros((S, d))
+        tables, infs = [], np.zeros((S, d))
+        for n in range(S):
+            row = []
+            for k in range(d):
+                msd, m, o = spec[n][k]
+                if o not in (0, 1):
+                    raise ValueError(f"ss_order should be in {{0, 1}}; was {o} (state {n}, dimension {k})")
+                order[n, k] = int(o)
+                mean[n, k] = float(m)
+                if not np.isfinite(mean[n, k]):
+                    raise ValueError(f"the mean of state {n}, dimension {k} is not finite")
+                if callable(msd):
+                    vals, inf = _tabulate(msd, o, MAX_T)
+                else:
+                    a = np.asarray(msd, dtype=np.float64)
+                    if a.ndim != 1 or len(a) < (2 if o == 0 else 1):
+                        raise ValueError(f"the MSD array of state {n}, dimension {k} must be 1-d: the lags 0, 1, ..."
+                                         + (" and msd(inf) last" if o == 0 else ""))
+                    vals, inf = (a[:-1], float(a[-1])) if o == 0 else (a, 0.0)
+                if not np.all(np.isfinite(vals)) or not np.isfinite(inf):
+                    raise ValueError(f"the MSD of state {n}, dimension {k} is not finite at every lag" +
+                                     (" and at infinity" if o == 0 else ""))
+                row.append(vals)
+                infs[n, k] = inf
+            tables.append(row)
+        n_lags = min(len(v) for row in tables for v in row)
+        self.state_spec = spec
+        self.msd = np.array([[v[:n_lags] for v in row] for row in tables])     # (S, d, n_lags)
+        self.msd_inf = infs
+        self.mean = mean
+        self.ss_order = order
+        self.init_transitions(S)
+        self._handle = None
+        self._trajsets = OrderedDict()
+
+    # ------------------------------------------------------------------ interface
+    @property
+    def d(self):
+        return self.msd.shape[1]
+
+    @property
+    def max_T(self):
+        """ the longest trajectory the model can evaluate: its MSD lags, at most 2048 frames """
+        return min(MAX_T, self.msd.shape[2])
+
+    def initial_loopingprofile(self, traj):
+        raise NotImplementedError
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_handle'] = None
+        state['_trajsets'] = OrderedDict()
+        return state
+
+    def invalidate(self):
+        """ call after changing the MSD tables, means or orders in place """
+        self._handle = None
+        self._trajsets.clear()
+
+    def handle(self):
+        if self._handle is None:
+            self._handle = _lib.GaussModelHandle(self.ss_order, self.mean, self.msd, self.msd_inf)
+        return self._handle
+
+    def _get_noise(self, traj):
+        return np.zeros(0)      # no localization error: it is part of the MSDs
+
+    _fingerprints = MultiStateRouse._fingerprints
+
+    def trajset(self, trajs):
+        """
+        Device-resident trajectories with their interval tables, built at the first use of a trajectory (or list of
+        them) and cached like `MultiStateRouse.trajset`: keyed by the identity of the trajectory objects and guarded by
+        their address, shape and content.  Raises before any device work for trajectories beyond `max_T` frames.
+        """
+        single = not isinstance(trajs, (list, tuple))
+        items = (trajs,) if single else tuple(trajs)
+        prints, arrs = self._fingerprints(items)
+        for a in arrs:
+            if a.ndim != 2 or a.shape[1] != self.d:
+                raise ValueError(f"trajectory shape {a.shape} does not match the model's d = {self.d}")
+            if len(a) > self.max_T:
+                raise ValueError(f"trajectory of {len(a)} frames: GenericGaussianModel evaluates at most {self.max_T} "
+                                 f"(the GPU tables take up to {MAX_T} frames, the MSD tables cover {self.msd.shape[2]} lags)")
+        key = tuple(id(t) if p[0] is not None else p for t, p in zip(items, prints))
+        hit = self._trajsets.get(key)
+        if hit is not None:
+            ts, kept, old_prints = hit
+            if all(a is b or p[0] is None for a, b, p in zip(kept, items, prints)) and old_prints == prints:
+                self._trajsets.move_to_end(key)
+                return ts
+        ts = _lib.GaussTrajSetHandle(self.handle(), arrs)
+        self._trajsets[key] = (ts, items, prints)
+        while len(self._trajsets) > 8:
+            self._trajsets.popitem(last=False)
+        return ts
+
+    # ------------------------------------------------------------------ likelihood
+    def logL(self, profile, traj):
+        """ log p(traj | profile, model) (reference bild/models.py:608-663) """
+        states = np.asarray(profile[:])
+        assert len(states) == len(traj)
+        return float(self.logL_batch(states[None, :], traj)[0])
+
+    def logL_batch(self, profiles, traj):
+        """ many expanded profiles on one trajectory: (n, T) int array or list of Loopingprofile -> (n,) """
+        if not isinstance(profiles, np.ndarray):
+            profiles = np.stack([np.asarray(p[:]) for p in profiles])
+        seg_start, seg_state = segments_from_states(profiles)
+        return _lib.gauss_logl_segments(self.handle(), self.trajset(traj), seg_start, seg_state)
+
+    def logL_st_batch(self, ss, thetas, traj):
+        """ one AMIS batch in the sampler's (s, theta) parametrisation (reference FixedkSampler.logL) """
+        return _lib.gauss_logl_st(self.handle(), self.trajset(traj), ss, thetas)
+
+    def logL_st(self, s, theta, traj):
+        return float(self.logL_st_batch(np.asarray(s)[None, :], np.asarray(theta)[None, :], traj)[0])
+
+    def logL_segments(self, seg_start, seg_state, trajs, traj_id=None):
+        """ general batch: run-length encoded profiles over a set of trajectories """
+        return _lib.gauss_logl_segments(self.handle(), self.trajset(trajs), seg_start, seg_state, traj_id)
+
+    # ------------------------------------------------------------------ generative model
+    def trajectory_from_loopingprofile(self, profile, missing_frames=None, rng=None):
+        """
+        Sample a trajectory (reference bild/models.py:665-728): interval by interval, each dimension from its state's
+        process, conditioned on the previous interval's last point (ss_order 0) or continuing from it (ss_order 1).
+
+        missing_frames : None, a fraction in (0, 1), a number of frames, or an array of frame indices
+        rng : numpy Generator (default: a fresh one)
+        """
+        rng = np.random.default_rng() if rng is None else rng
+        T = len(profile)
+        if T > self.msd.shape[2]:
+            raise ValueError(f"profile of {T} frames: the MSD tables cover {self.msd.shape[2]} lags")
+        if missing_frames is None or (np.isscalar(missing_frames) and missing_frames == 0):
+            missing = np.array([], dtype=int)
+        elif np.isscalar(missing_frames):
+            if 0 < missing_frames < 1:
+                missing = np.nonzero(rng.random(T) < missing_frames)[0]
+            else:
+                missing = rng.choice(T, size=int(missing_frames), replace=False).astype(int)
+        else:
+            missing = np.asarray(missing_frames, dtype=int)
+
+        ivs = profile.intervals()
+        ivs[-1] = (ivs[-1][0], T, ivs[-1][2])
+        snippets = []
+        for i, (t0, t1, n) in enumerate(ivs):
+            t_start = 0 if i == 0 else t0 - 1
+            snippets.append([])
+            for k in range(self.d):
+                ti = np.arange(t_start, t1)
+                m, o = self.mean[n, k], self.ss_order[n, k]
+                C = covariance(self.msd[n, k], self.msd_inf[n, k], ti, o)
+                cont = o == 0 and i > 0
+                if cont:
+                    mu = (snippets[i - 1][k][-1] - m) * C[1:, 0] / C[0, 0]
+                    C = (C - C[:, [0]] * C[[0], :] / C[0, 0])[1:, 1:]
+                x = (np.linalg.cholesky(C) @ rng.standard_normal(len(C)) if len(C) else np.zeros(0)) + m
+                if cont:
+                    x = x + mu
+                if o == 0:
+                    snippets[i].append(x)
+                elif i == 0:
+                    snippets[i].append(np.insert(np.cumsum(x), 0, 0))
+                else:
+                    snippets[i].append(snippets[i - 1][k][-1] + np.cumsum(x))
+        data = np.concatenate([np.array(snip).T for snip in snippets])
+        data[missing] = np.nan
+        return Trajectory(data, loopingprofile=profile)

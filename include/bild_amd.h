@@ -570,6 +570,50 @@ int bild_run_totals(const bild_run *r, int64_t *totals);
 int bild_interval_marginals(int64_t P, int k1, int n, int64_t T, const int32_t *seg_start,
                             const int32_t *seg_state, const double *w, double *post);
 
+/* ---------------------------------------------------------------- GenericGaussianModel -------
+ * The reference's model-agnostic Gaussian model (bild/models.py:536-728): every state n and dimension k is a Gaussian
+ * process given by its MSD, its mean m and its steady-state order (0: the positions are stationary, 1: the increments
+ * are).  The likelihood of a profile is a sum over its intervals of the Gaussian log-density of the interval's window:
+ * [0, t1) for the first interval, [t0 - 1, t1) for the others, valid frames only, per dimension; ss_order 0 conditions a
+ * later interval on the first valid value of its window (taken raw, as the reference does), ss_order 1 uses the
+ * increments between consecutive valid frames, minus m.  A later ss_order-0 interval whose window has no valid frame in
+ * some dimension (the reference raises IndexError) makes that candidate's result NaN.  Derivation, covariance rule and
+ * costs: DESIGN.md, "GenericGaussianModel".
+ *
+ * A trajectory set builds, for every trajectory and state, the term of every window [a, b) (T (T + 1) / 2 doubles) and
+ * of every first interval (T + 1), summed over the dimensions in index order; an evaluation is k + 1 reads of those.
+ * Results are a pure function of (candidate, trajectory set): bit-identical whatever the batch, its order and the entry
+ * point. */
+typedef struct bild_gauss_model bild_gauss_model;
+typedef struct bild_gauss_trajset bild_gauss_trajset;
+
+/* S states, d dimensions; per (state, dimension) i = s*d + k: ss_order[i] in {0, 1}, mean[i], the MSD at the integer
+ * lags 0 .. Tmax (msd[i*(Tmax+1) + lag]) and its limit msd_inf[i] (read for ss_order 0 only).  Host memory only: needs
+ * no GPU. */
+int bild_gauss_model_create(int S, int d, int Tmax, const int32_t *ss_order, const double *mean, const double *msd,
+                            const double *msd_inf, bild_gauss_model **out);
+int bild_gauss_model_destroy(bild_gauss_model *m);
+
+/* n_traj trajectories of T[j] frames each (1 <= T[j] <= 2048, T[j] - 1 <= Tmax), x: their T[j] x d values one after the
+ * other, row-major, NaN = missing.  Uploads them and builds the tables before it returns (BILD_ERR_UNSUPPORTED beyond
+ * 2048 frames).  The model must outlive the set. */
+int bild_gauss_trajset_create(const bild_gauss_model *m, int n_traj, const int32_t *T, const double *x,
+                              bild_gauss_trajset **out);
+int bild_gauss_trajset_destroy(bild_gauss_trajset *ts);
+/* device bytes of the set's tables, and the wall time of their build in ms; either pointer may be NULL */
+int bild_gauss_trajset_info(const bild_gauss_trajset *ts, int64_t *table_bytes, double *build_ms);
+
+/* Evaluation, host buffers in and out, synchronous.  Segments as for bild_logl_segments (first start 0, later starts
+ * >= 1 and non-decreasing, states < S; empty segments and boundaries between equal states are dropped, so the intervals
+ * are the runs of equal state); traj_id may be NULL (all rows on trajectory 0). */
+int bild_gauss_logl_segments(const bild_gauss_model *m, const bild_gauss_trajset *ts, int64_t n, int K1,
+                             const int32_t *seg_start, const int32_t *seg_state, const int32_t *traj_id, double *out);
+/* the sampler's (s, theta) rows as bild_logl_st takes them; the switch frames are computed on the device with the same
+ * operations as FixedkSampler.st2profile.  A row that is no point on the simplex or names a state >= S gets NaN and the
+ * call returns BILD_ERR_INVALID (the other rows' results are written all the same). */
+int bild_gauss_logl_st(const bild_gauss_model *m, const bild_gauss_trajset *ts, int64_t n, int K1, const double *ss,
+                       const int64_t *thetas, const int32_t *traj_id, double *out);
+
 #ifdef __cplusplus
 }
 #endif
