@@ -138,6 +138,9 @@ _SIGNATURES = {
     'bild_gauss_trajset_info': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
     'bild_gauss_logl_segments': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, _dp]),
     'bild_gauss_logl_st': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _dp, _vp, _ip, _dp]),
+    # Rouse trajectory generator (sim.cpp)
+    'bild_rouse_simulate': (ctypes.c_int, [ctypes.c_int] * 3 + [_dp] * 7 + [ctypes.c_int, _ip, ctypes.c_int, _ip, _ip, _vp, _dp, _dp,
+                                           ctypes.c_uint64, ctypes.c_int64, _dp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -374,6 +377,37 @@ def gauss_logl_st(model, ts, ss, thetas, traj_id=None):
     assert tid is None or tid.shape == (n,)
     out = np.empty(n, dtype=np.float64)
     check(lib().bild_gauss_logl_st(model._h, ts._h, n, K1, dptr(ss), aptr(thetas), iptr(tid), dptr(out)))
+    return out
+
+
+def rouse_simulate(V, b, sqrt_sig, sqrt_cinf, VtG, VtM0, w, T, seg_start, seg_state, missing, loc_err, normals=None, seed=0,
+                   scratch_bytes=0):
+    """
+    Rouse trajectories in modal coordinates (bild_rouse_simulate): per state V (S, N, N), b, sqrt_sig, sqrt_cinf (S, N),
+    VtG, VtM0 (S, N, d); w (N,); per trajectory T (n,), segments (n, K1), missing (sum T,) bool or None, loc_err (n, d);
+    normals: the host-drawn normals of every trajectory in order (replay), or None (device mode, keyed by ``seed``).
+    ``scratch_bytes`` bounds the upload chunks of the normals (0: the library's rule).  -> (sum T, d) float64
+    """
+    V, b, sqrt_sig, sqrt_cinf, VtG, VtM0, w = (f64(a) for a in (V, b, sqrt_sig, sqrt_cinf, VtG, VtM0, w))
+    S, N, d = VtG.shape
+    assert V.shape == (S, N, N) and b.shape == sqrt_sig.shape == sqrt_cinf.shape == (S, N) and VtM0.shape == (S, N, d)
+    assert w.shape == (N,)
+    T, seg_start, seg_state = i32(T), i32(seg_start), i32(seg_state)
+    n = T.shape[0]
+    K1 = seg_start.shape[1] if seg_start.ndim == 2 else 1
+    assert seg_start.shape == seg_state.shape == (n, K1)
+    rows = int(T.sum())
+    miss = None if missing is None else np.ascontiguousarray(missing, dtype=np.uint8)
+    assert miss is None or miss.shape == (rows,)
+    err = f64(loc_err)
+    assert err.shape == (n, d)
+    z = None if normals is None else f64(normals)
+    assert z is None or z.shape == (rows * (N + 1) * d,)
+    out = np.empty((rows, d), dtype=np.float64)
+    check(lib().bild_rouse_simulate(S, N, d, dptr(V), dptr(b), dptr(sqrt_sig), dptr(sqrt_cinf), dptr(VtG), dptr(VtM0), dptr(w),
+                                    n, iptr(T), K1, iptr(seg_start), iptr(seg_state), None if miss is None else aptr(miss),
+                                    dptr(err), None if z is None else dptr(z), int(seed), int(scratch_bytes),
+                                    dptr(out) if rows else None))
     return out
 
 

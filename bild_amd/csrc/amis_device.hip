@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "amis_math.h"
+#include "philox.h"
 
 namespace bild {
 namespace {
@@ -177,72 +178,7 @@ __global__ void __launch_bounds__(kAmisBlock) pass_c_kernel(AmisView v, int64_t 
 // the samplers of one adaptive-k run, which share the user's seed, on distinct streams; gamma variates by Marsaglia-Tsang (with the boost gamma(a) = gamma(a + 1) U^(1/a) below one), the
 // Dirichlet point as their normalised vector, the trace slot by slot from the CFC weights as bild_amis_sample_traces does.
 // Not the reference's random numbers -- the same sampler in distribution (tests: evidences agree within their errors).
-struct Philox {
-    uint32_t c[4], k[2];
-    uint32_t out[4];
-    int have;
-    __device__ Philox(uint64_t seed, uint64_t stream, uint64_t sample)
-    {
-        c[0] = (uint32_t)sample;
-        c[1] = (uint32_t)(sample >> 32);
-        c[2] = (uint32_t)stream;
-        c[3] = 0; // block counter of this stream
-        k[0] = (uint32_t)seed;
-        k[1] = (uint32_t)(seed >> 32);
-        have = 0;
-    }
-    __device__ void block()
-    {
-        uint32_t x0 = c[0], x1 = c[1], x2 = c[2], x3 = c[3], k0 = k[0], k1 = k[1];
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            const uint64_t p0 = (uint64_t)0xD2511F53u * x0, p1 = (uint64_t)0xCD9E8D57u * x2;
-            const uint32_t y0 = (uint32_t)(p1 >> 32) ^ x1 ^ k0, y1 = (uint32_t)p1, y2 = (uint32_t)(p0 >> 32) ^ x3 ^ k1, y3 = (uint32_t)p0;
-            x0 = y0;
-            x1 = y1;
-            x2 = y2;
-            x3 = y3;
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        out[0] = x0;
-        out[1] = x1;
-        out[2] = x2;
-        out[3] = x3;
-        ++c[3];
-        have = 2;
-    }
-    // uniform in [0, 1) with 53 random bits
-    __device__ double uniform()
-    {
-        if (!have) block();
-        --have;
-        const uint64_t bits = ((uint64_t)out[2 * have] << 32) | out[2 * have + 1];
-        return (double)(bits >> 11) * 0x1p-53;
-    }
-    __device__ double normal() // Box-Muller, one of the pair
-    {
-        const double u1 = 1.0 - uniform(), u2 = uniform(); // u1 in (0, 1]
-        return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
-    }
-    __device__ double gamma(double a)
-    {
-        if (!(a > 0)) return 0.0;
-        double boost = 1.0;
-        if (a < 1.0) { // gamma(a) = gamma(a + 1) U^(1/a)
-            boost = pow(1.0 - uniform(), 1.0 / a);
-            a += 1.0;
-        }
-        const double d = a - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * d);
-        for (int it = 0; it < 64; ++it) { // (acceptance > 95 % per trial)
-            const double x = normal(), t = 1.0 + cc * x;
-            if (t <= 0) continue;
-            const double v = t * t * t, u = 1.0 - uniform();
-            if (u < 1.0 - 0.0331 * (x * x) * (x * x) || log(u) < 0.5 * x * x + d * (1.0 - v + log(v))) return boost * d * v;
-        }
-        return boost * d;
-    }
-};
+// (struct Philox: philox.h)
 
 // one sample per lane: ss (N x k1) and the states (N x k1 bytes) written where the likelihood and the passes read them
 __global__ void __launch_bounds__(256) draw_kernel(int k1, int n, int64_t N, uint64_t seed, uint64_t first, const double *__restrict__ a,

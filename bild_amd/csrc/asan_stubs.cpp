@@ -52,3 +52,7 @@ int launch_gauss_walk(const GaussWalk &, bool, void *) { return 1; }
 namespace bild {
 int launch_exchange(const ExParams &, void *) { return 1; }
 } // namespace bild
+#include "sim.h"
+namespace bild {
+int launch_rouse_simulate(const SimParams &, void *) { return 1; }
+} // namespace bild

@@ -324,26 +324,9 @@ class MultiStateRouse(MultiStateModel):
         missing frames, then add localization noise.
         """
         rng = np.random.default_rng() if rng is None else rng
-        if localization_error is None:
-            if self.localization_error is None:
-                raise ValueError("Need to specify either localization_error or model.localization_error")
-            localization_error = self.localization_error
-        if np.isscalar(localization_error):
-            localization_error = self.d * [localization_error]
-        localization_error = np.asarray(localization_error, dtype=np.float64)
-        if localization_error.shape != (self.d,):
-            raise ValueError("Did not understand localization_error")
-
+        localization_error = _localization_error(self, localization_error)
         T = len(profile)
-        if missing_frames is None or (np.isscalar(missing_frames) and missing_frames == 0):
-            missing = np.array([], dtype=int)
-        elif np.isscalar(missing_frames):
-            if 0 < missing_frames < 1:
-                missing = np.nonzero(rng.random(T) < missing_frames)[0]
-            else:
-                missing = rng.choice(T, size=int(missing_frames), replace=False).astype(int)
-        else:
-            missing = np.asarray(missing_frames, dtype=int)
+        missing = _missing_frames(missing_frames, T, rng)
 
         data = np.full((T, self.d), np.nan)
         conf = self.models[profile[0]].conf_ss(rng)
@@ -354,6 +337,166 @@ class MultiStateRouse(MultiStateModel):
         data[missing, :] = np.nan
         data += localization_error[None, :] * rng.standard_normal(data.shape)
         return Trajectory(data, localization_error=localization_error, loopingprofile=profile)
+
+    def trajectories_from_loopingprofiles(self, profiles, localization_error=None, missing_frames=None, rng=None, seed=None):
+        """
+        Many trajectories at once, generated on the GPU in each state's modal coordinates.
+
+        profiles : sequence of `Loopingprofile` or 1-d integer arrays (lengths may differ), or an (n, T) integer array
+        localization_error : as for `trajectory_from_loopingprofile`
+        missing_frames : one of that method's forms (None, a fraction, a count, an index array -- as a NumPy array),
+            applied to every trajectory, or a list / tuple with one such entry per trajectory
+        rng : numpy Generator -- replay mode: the host draws exactly the numbers that
+            ``[self.trajectory_from_loopingprofile(p, localization_error, missing_frames, rng=rng) for p in profiles]``
+            draws, in the same order, and leaves ``rng`` where that loop would; the results equal the loop's to rounding.
+        seed : int in [0, 2**64) -- device mode (also when neither ``rng`` nor ``seed`` is given, with a fresh seed): the
+            normals come from a counter-based generator on the device; trajectory ``i`` is a pure function of
+            (seed, i, its profile, its missing frames), and its missing frames are drawn from
+            ``np.random.default_rng([seed, i])``.
+
+        Returns
+        -------
+        list of `Trajectory`, one per profile and in order
+        """
+        if rng is not None and seed is not None:
+            raise ValueError("give either rng (replay mode) or seed (device mode), not both")
+        if self.models is None:
+            raise ValueError("this model was built from arrays (from_arrays / from_reference): it has no per-state eigenbasis, "
+                             "so it cannot generate trajectories (trajectory_from_loopingprofile cannot either)")
+        items = list(profiles)
+        states = [np.asarray(p[:]) for p in items]
+        S = self.nStates
+        for i, st in enumerate(states):
+            if st.ndim != 1 or len(st) < 1 or not np.issubdtype(st.dtype, np.integer):
+                raise ValueError(f"profile {i} is not a non-empty 1-d integer array")
+            if st.min() < 0 or st.max() >= S:
+                raise ValueError(f"profile {i} has a state outside 0 .. {S - 1}")
+        err = _localization_error(self, localization_error)
+        n = len(states)
+        if isinstance(missing_frames, (list, tuple)):
+            if len(missing_frames) != n:
+                raise ValueError(f"missing_frames has {len(missing_frames)} entries for {n} profiles")
+            specs = list(missing_frames)
+        else:
+            specs = [missing_frames] * n
+        if seed is not None:
+            seed = int(seed)
+            if not 0 <= seed < 2 ** 64:
+                raise ValueError("seed must be an integer in [0, 2**64)")
+        if n == 0:
+            return []
+
+        arrs = self._modal_arrays()
+        T = np.array([len(st) for st in states], dtype=np.int64)
+        seg_start, seg_state = _ragged_segments(states, T)
+        errs = np.tile(err, (n, 1))
+        N, d = self.measurement.shape[0], self.d
+        offs = np.concatenate([[0], np.cumsum(T)])
+
+        if rng is None:     # device mode
+            mask = np.zeros(int(offs[-1]), dtype=bool)
+            if seed is None:
+                seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+            for i, spec in enumerate(specs):
+                if not _missing_is_none(spec):
+                    drawn = np.isscalar(spec)
+                    mask[offs[i]:offs[i + 1]][_missing_frames(spec, int(T[i]), np.random.default_rng([seed, i]) if drawn else None)] = True
+            data = _lib.rouse_simulate(*arrs, self.measurement, T, seg_start, seg_state, mask, errs, seed=seed)
+        else:               # replay mode: host groups of at most _REPLAY_GROUP_BYTES of normals
+            per = T * (N + 1) * d
+            data = np.empty((int(offs[-1]), d))
+            i0 = 0
+            while i0 < n:
+                i1 = i0 + 1
+                while i1 < n and per[i0:i1 + 1].sum() * 8 <= _REPLAY_GROUP_BYTES:
+                    i1 += 1
+                mask, z = _replay_draws(specs[i0:i1], T[i0:i1], N, d, rng)
+                data[offs[i0]:offs[i1]] = _lib.rouse_simulate(*arrs, self.measurement, T[i0:i1], seg_start[i0:i1],
+                                                              seg_state[i0:i1], mask, errs[i0:i1], normals=z)
+                i0 = i1
+        return [Trajectory(data[offs[i]:offs[i + 1]], localization_error=err.copy(), loopingprofile=items[i]) for i in range(n)]
+
+    def _modal_arrays(self):
+        """ per state, stacked: V, b, sqrt(sig), sqrt(cinf), V^T G, V^T M0 -- what bild_rouse_simulate takes """
+        out = [[] for _ in range(6)]
+        for m in self.models:
+            V, b, sig, cinf = m.modal_dynamics()
+            for lst, a in zip(out, (V, b, np.sqrt(np.maximum(sig, 0.)), np.sqrt(np.maximum(cinf, 0.)),
+                                    V.T @ m._dynamics['G'], V.T @ m._dynamics['M0'])):
+                lst.append(a)
+        return [np.ascontiguousarray(np.stack(lst), dtype=np.float64) for lst in out]
+
+
+# replay mode: host memory of the normals handed to the library in one call
+_REPLAY_GROUP_BYTES = 256 << 20
+
+
+def _localization_error(model, localization_error):
+    """ the localization error a generator call uses (MultiStateRouse.trajectory_from_loopingprofile's rules) -> (d,) """
+    if localization_error is None:
+        if model.localization_error is None:
+            raise ValueError("Need to specify either localization_error or model.localization_error")
+        localization_error = model.localization_error
+    if np.isscalar(localization_error):
+        localization_error = model.d * [localization_error]
+    localization_error = np.asarray(localization_error, dtype=np.float64)
+    if localization_error.shape != (model.d,):
+        raise ValueError("Did not understand localization_error")
+    return localization_error
+
+
+def _missing_is_none(spec):
+    return spec is None or (np.isscalar(spec) and spec == 0)
+
+
+def _missing_frames(spec, T, rng):
+    """ the missing frames of one trajectory, drawn from ``rng`` as trajectory_from_loopingprofile draws them """
+    if _missing_is_none(spec):
+        return np.array([], dtype=int)
+    if np.isscalar(spec):
+        if 0 < spec < 1:
+            return np.nonzero(rng.random(T) < spec)[0]
+        return rng.choice(T, size=int(spec), replace=False).astype(int)
+    return np.asarray(spec, dtype=int)
+
+
+def _replay_draws(specs, T, N, d, rng):
+    """
+    What the loop of trajectory_from_loopingprofile draws from ``rng`` for trajectories of lengths T, in its order: per
+    trajectory the missing frames, N d normals of the steady state, (T - 1) N d of the steps, T d of the localization
+    noise.  -> (missing mask (sum T,) bool, normals (sum T (N + 1) d,)), as bild_rouse_simulate takes them
+    """
+    T = np.asarray(T, dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(T)])
+    per = T * (N + 1) * d
+    mask = np.zeros(int(offs[-1]), dtype=bool)
+    z = np.empty(int(per.sum()))
+    zo = 0
+    for i, spec in enumerate(specs):
+        mask[offs[i]:offs[i + 1]][_missing_frames(spec, int(T[i]), rng)] = True
+        rng.standard_normal(out=z[zo:zo + per[i]])
+        zo += per[i]
+    return mask, z
+
+
+def _ragged_segments(states, T):
+    """ profiles of lengths T -> run-length segments (n, K1) int32, padded with empty segments at T[i] """
+    n = len(states)
+    flat = np.concatenate(states)
+    offs = np.concatenate([[0], np.cumsum(T)])
+    change = np.ones(len(flat), dtype=bool)
+    change[1:] = flat[1:] != flat[:-1]
+    change[offs[:-1]] = True
+    idx = np.flatnonzero(change)
+    owner = np.searchsorted(offs, idx, side='right') - 1
+    nseg = np.bincount(owner, minlength=n)
+    K1 = int(nseg.max())
+    rank = np.arange(len(idx)) - np.repeat(np.cumsum(nseg) - nseg, nseg)
+    seg_start = np.repeat(np.asarray(T, dtype=np.int32)[:, None], K1, axis=1)
+    seg_state = np.zeros((n, K1), dtype=np.int32)
+    seg_start[owner, rank] = idx - offs[owner]
+    seg_state[owner, rank] = flat[idx]
+    return seg_start, seg_state
 
 
 class FactorizedModel(MultiStateModel):

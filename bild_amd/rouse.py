@@ -105,6 +105,8 @@ class Model:
             X = (V * diag) @ V.T
             return 0.5 * (X + X.T)
 
+        # the eigenbasis itself, for the modal generator (modal_dynamics); kept out of _dynamics, which callers read by key
+        self._modal = (V, b, sig, cinf)
         self._dynamics = {
             'needs_updating': False,
             'N': self.N, 'D': self.D, 'k': self.k, 'd': self.d,
@@ -123,6 +125,16 @@ class Model:
             if not run_if_necessary:
                 raise RuntimeError("Model changed since last call to update_dynamics()")
             self.update_dynamics()
+
+    def modal_dynamics(self):
+        """
+        -> (V (N, N), b (N,), sig (N,), cinf (N,)): the orthonormal eigenbasis (columns = modes) in which the dynamics are
+        diagonal, ``B = V diag(b) V^T``, ``LSig = V diag(sqrt(sig))``, ``LC0 = V diag(sqrt(cinf))``
+        """
+        self.check_dynamics()
+        if getattr(self, '_modal', None) is None:     # a model pickled before the basis was kept
+            self.update_dynamics()
+        return tuple(a.copy() for a in self._modal)
 
     def steady_state(self):
         """ -> (M (N, d), C (N, N)) ; reference call sites pyx:160, models.py:366 """

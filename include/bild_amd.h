@@ -614,6 +614,32 @@ int bild_gauss_logl_segments(const bild_gauss_model *m, const bild_gauss_trajset
 int bild_gauss_logl_st(const bild_gauss_model *m, const bild_gauss_trajset *ts, int64_t n, int K1, const double *ss,
                        const int64_t *thetas, const int32_t *traj_id, double *out);
 
+/* ---------------------------------------------------------------- Rouse trajectory generator -------
+ * n trajectories of the multi-state Rouse model (MultiStateRouse.trajectories_from_loopingprofiles), computed in each
+ * state's modal coordinates: per state s an orthonormal eigenbasis V[s] (N x N, row = monomer, column = mode) with
+ * B = V diag(b) V^T, Sig = V diag(sqrt_sig^2) V^T, C0 = V diag(sqrt_cinf^2) V^T, and VtG[s] = V^T G, VtM0[s] = V^T M0
+ * (N x d); w (N) is the measurement vector.  Derivation: DESIGN.md section 11.
+ *
+ * Trajectory i has T[i] >= 1 frames and the profile given by its segments (n x K1, as bild_logl_segments takes them: first
+ * start 0, later starts >= 1 and non-decreasing, states < S; starts >= T[i] pad).  Frame 0 is drawn from the steady state
+ * of its state, frame t >= 1 propagates with the state in force at t.  missing (sum T bytes, may be NULL) marks frames to
+ * return as NaN; loc_err (n x d) scales the localization noise.  out receives the sum T x d values, trajectory after
+ * trajectory, row-major.
+ *
+ * normals != NULL (replay): per trajectory, one after the other, T N d normals of the dynamics (frame, mode, dimension;
+ * frame 0 the steady state) and then T d of the localization noise -- the order in which
+ * MultiStateRouse.trajectory_from_loopingprofile draws them.  They are uploaded in chunks of whole trajectories within
+ * scratch_bytes, or, when that is 0, within min(1 GiB, a third of the free device memory); a trajectory that alone
+ * exceeds the budget: BILD_ERR_UNSUPPORTED.  normals == NULL (device mode): the normals are a pure function of (seed,
+ * index i of the trajectory in the call, frame, mode, dimension), those of the localization noise of (seed, i, frame,
+ * dimension) -- Philox-4x32-10, one Box-Muller pair per two frames (sim.hip) --, so trajectory i does not depend on the
+ * other trajectories of the call.  Synchronous.  BILD_ERR_UNSUPPORTED when N > 256 or d > 8. */
+int bild_rouse_simulate(int S, int N, int d, const double *V, const double *b, const double *sqrt_sig,
+                        const double *sqrt_cinf, const double *VtG, const double *VtM0, const double *w, int n,
+                        const int32_t *T, int K1, const int32_t *seg_start, const int32_t *seg_state,
+                        const uint8_t *missing, const double *loc_err, const double *normals, uint64_t seed,
+                        int64_t scratch_bytes, double *out);
+
 #ifdef __cplusplus
 }
 #endif
