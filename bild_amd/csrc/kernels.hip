@@ -99,6 +99,26 @@ __device__ __forceinline__ void fmac_bcast(double &acc, double x, double w)
 // orders every later reader of x behind two wait states after its producer
 __device__ __forceinline__ void dpp_ready(double &x) { asm volatile("s_nop 1" : "+v"(x)); }
 
+// Row PAIR (the two-row frame of the listed loop): rows 2p and 2p + 1 of the wavefront run one task.  v_permlane16_swap exchanges
+// the odd rows of its first operand with the even rows of its second; with x as both operands the first result holds the even
+// row's x in both rows, the second the odd row's.
+__device__ __forceinline__ void pair_swap(double x, double &even, double &odd)
+{
+    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
+    const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    even = __hiloint2double((int)h[0], (int)l[0]);
+    odd = __hiloint2double((int)h[1], (int)l[1]);
+}
+// the odd rows take x of lane + 1 of their row, the even rows keep their own (DPP row_shl:1, written in the odd rows only)
+__device__ __forceinline__ double odd_rows_shift(double x)
+{
+    const int lo = __double2loint(x), hi = __double2hiint(x);
+    const int l = __builtin_amdgcn_update_dpp(lo, lo, 0x101, 0xA, 0xF, false);
+    const int h = __builtin_amdgcn_update_dpp(hi, hi, 0x101, 0xA, 0xF, false);
+    return __hiloint2double(h, l);
+}
+
 template <int NP, int I = 0>
 struct RowOps {
     // sa += sum over even i of x[lane i] w[i], sb likewise over odd i (the order of the packed layouts)
@@ -120,6 +140,27 @@ template <int NP>
 struct RowOps<NP, NP> {
     static __device__ __forceinline__ void dot(double &, double &, double, const double (&)[NP]) {}
     static __device__ __forceinline__ void rank1(double (&)[NP], double, double) {}
+};
+// the same for a row of a PAIR, which holds entries 2k + (row odd) as its entry k: x is the row's (C w) as shifted by
+// odd_rows_shift, so that lane 2k of the row holds entry 2k + (row odd) in both rows
+template <int NP, int K = 0>
+struct PairOps {
+    // s += sum over the row's entries i of x[i] w[i], i ascending (sa of RowOps::dot in the even row, sb in the odd one)
+    static __device__ __forceinline__ void dot(double &s, double x, const double (&w)[NP])
+    {
+        fmac_bcast<2 * K>(s, x, w[K]);
+        PairOps<NP, K + 1>::dot(s, x, w);
+    }
+    static __device__ __forceinline__ void rank1(double (&col)[NP / 2], double x, double c)
+    {
+        fmac_bcast<2 * K>(col[K], x, c);
+        PairOps<NP, K + 1>::rank1(col, x, c);
+    }
+};
+template <int NP>
+struct PairOps<NP, NP / 2> {
+    static __device__ __forceinline__ void dot(double &, double, const double (&)[NP]) {}
+    static __device__ __forceinline__ void rank1(double (&)[NP / 2], double, double) {}
 };
 
 // log() is needed once per task; out of line, so that its polynomial constants are not hoisted
@@ -243,7 +284,11 @@ __device__ __forceinline__ void matvec_to_lds(XPtr X, const Cols<NP, CPL> &in, d
 // that can: what a builder needs (entries, state records) stays out of the evaluating kernels, and what they need (tails, walk plan,
 // landing on tables that do not exist yet) out of the builders.  (The tail code of round 4 cost the builders 70 % while it was
 // compiled into both: configs[3] tables 234 -> 406 ms.)
-template <int NP, int CPL, int G, int W, int OCC, int LAY, int MODE, int FLAVOR, bool DUMP, bool JUMP, bool BUILD>
+// PAIR: the two-row frame of the listed loop (LAY 3 only, see logl_kernel): a task runs on a pair of rows, lane j of the even
+// row holds the even entries of column j of [C | M], the odd row the odd ones -- half the predict, dot and rank-1 instructions of
+// a frame.  Everything else (prologue, events, epilogue) runs in both rows alike on whole columns, unpacked from the halves at an
+// event and packed again behind it; both rows then hold the same bits, so they take the same branches.
+template <int NP, int CPL, int G, int W, int OCC, int LAY, int MODE, int FLAVOR, bool DUMP, bool JUMP, bool BUILD, bool PAIR = false>
 __device__ __forceinline__ void logl_body(const KParams &p)
 {
     constexpr bool HASG = FLAVOR == 0;
@@ -275,6 +320,12 @@ __device__ __forceinline__ void logl_body(const KParams &p)
     const int wv = tid >> 6;
     const int grp = BLK ? ((lane >> 2) & 3) : lane / G;
     const int gl = BLK ? ((lane & 3) | ((lane >> 4) << 2)) : lane - grp * G; // ROW: lane / 16, lane % 16
+    static_assert(!PAIR || (LAY == 3 && CPL == 1 && JUMP && !DUMP && !BUILD), "the row pair serves the listed frame loop only");
+    // tasks per wavefront, this lane's task among them, and its row of the pair (PAIR: each row keeps its own LDS areas)
+    constexpr int TPW = PAIR ? GPW / 2 : GPW;
+    const int tgrp = PAIR ? grp >> 1 : grp;
+    const int odd = PAIR ? (grp & 1) : 0;
+    const bool lead = gl == 0 && !odd; // the lane that writes the task's results
 
     // Work lists (walk.hip): this launch runs only the tasks the table walk handed on -- kWorkBuckets lists by expected
     // work, dealt out heaviest first.  Slot q of that order goes to (wave, row) so that the heaviest tasks get a wave
@@ -328,13 +379,13 @@ __device__ __forceinline__ void logl_body(const KParams &p)
     const int S = p.S;
     const int d = p.d;
     const int K1 = p.K1;
-    const int64_t gstride = (int64_t)gridDim.x * (kWaves * GPW);
+    const int64_t gstride = (int64_t)gridDim.x * (kWaves * TPW);
     const int64_t n_waves = (int64_t)gridDim.x * kWaves, wave_id = (int64_t)blockIdx.x * kWaves + wv;
     // (listed, and the list fits the rows of the grid: spread -- row j of wave w takes slot j * n_waves + w, every second
     // layer in reverse: the waves that carry the heaviest tasks of one layer get the lightest of the next, or none)
     const bool spread = listed && (BILD_SPREAD_ALWAYS || n_tasks <= gstride);
 
-    for (int64_t it = spread ? (int64_t)grp : wave_id * GPW + grp;; it += spread ? (int64_t)GPW : gstride) {
+    for (int64_t it = spread ? (int64_t)tgrp : wave_id * TPW + tgrp;; it += spread ? (int64_t)TPW : gstride) {
         int64_t task = it;
         if (spread) { // `it` counts layers of n_waves slots
             if (it * n_waves >= n_tasks) break;
@@ -380,16 +431,16 @@ __device__ __forceinline__ void logl_body(const KParams &p)
         const int tj = p.traj_id ? p.traj_id[r] : 0;
         const TrajDesc *__restrict__ td = p.trajs + tj;
         if (e >= td->dstar) {
-            if (gl == 0) p.out[otask] = 0.0;
+            if (lead) p.out[otask] = 0.0;
             continue;
         }
         const int T = td->T;
         const double s2 = td->s2[e];
         if (ROW) {
-            if (gl == 0) row_const[0] = s2;
+            if (gl == 0) row_const[0] = odd ? 0.0 : s2; // (PAIR: the S sum of the odd row starts from 0, see update)
             wave_lds_fence();
         }
-        double s2_now = s2; // ROW: read again from LDS at the top of every frame (see row_const)
+        double s2_now = odd ? 0.0 : s2; // ROW: read again from LDS at the top of every frame (see row_const)
         const int nd = td->ndims[e];
 
         bool isM[CPL];
@@ -528,6 +579,18 @@ __device__ __forceinline__ void logl_body(const KParams &p)
         double wown = 0.0; // block layout: w_c of the own covariance column, 0 for the other lanes
         auto load_state = [&](int st) {
             const double *__restrict__ sb = lds_hdr + (size_t)st * HDR; // lam | wq | sig at the offsets of the state block
+            if constexpr (PAIR) { // (the row's entries only: entry k of wq, L, sgd is entry 2k + odd)
+                const double mu = isC[0] ? sb[StateBlock::lam(NP) + cidx[0]] : (hasImg[0] ? 1.0 : 0.0);
+                const double sgc = isC[0] ? sb[StateBlock::sig(NP) + cidx[0]] : 0.0;
+#pragma unroll
+                for (int k = 0; k < NP / 2; ++k) {
+                    const int i = 2 * k + odd;
+                    wq[k] = sb[StateBlock::wq(NP) + i];
+                    L.v[0][k] = sb[StateBlock::lam(NP) + i] * mu;
+                    sgd[k] = (gl == i) ? sgc : 0.0;
+                }
+                return;
+            }
             if constexpr (!kWqFromLds) {
 #pragma unroll
                 for (int i = 0; i < NP; ++i) wq[i] = sb[StateBlock::wq(NP) + i];
@@ -555,6 +618,20 @@ __device__ __forceinline__ void logl_body(const KParams &p)
         // ---- initial condition: steady state of state profile[0] (pyx:160-163) ----
         // (a task that starts from a table -- every task of the jump instantiation -- loads its state there: start_from)
         Cols<NP, CPL> col;
+        // PAIR: the row's half of its column in the frame loop (entry k = entry 2k + odd of col); col itself is live at events only
+        double colh[PAIR ? NP / 2 : 1];
+        auto pack = [&]() {
+            if constexpr (PAIR) {
+#pragma unroll
+                for (int k = 0; k < NP / 2; ++k) colh[k] = odd ? col.v[0][2 * k + 1] : col.v[0][2 * k];
+            }
+        };
+        auto unpack = [&]() {
+            if constexpr (PAIR) {
+#pragma unroll
+                for (int k = 0; k < NP / 2; ++k) pair_swap(colh[k], col.v[0][2 * k], col.v[0][2 * k + 1]);
+            }
+        };
         if (JUMP && p.prefix != nullptr && !p.no_jump) {
 #pragma unroll
             for (int q = 0; q < CPL; ++q)
@@ -594,6 +671,33 @@ __device__ __forceinline__ void logl_body(const KParams &p)
             }
         };
         auto update = [&](const double (&xv)[CPL]) {
+            if constexpr (PAIR) {
+                // the row's half of every sum, then the two halves added in the order of the one-row frame (even + odd)
+                double a = 0.0;
+#pragma unroll
+                for (int k = 0; k < NP / 2; ++k) a = fma(wq[k], colh[k], a);
+                double a0, a1;
+                pair_swap(a, a0, a1);
+                const double ev = (a0 + a1) - xv[0];
+                double evs = odd_rows_shift(ev); // lane 2k of the row: (C w) entry 2k + odd
+                dpp_ready(evs);
+                double sr = s2_now; // (s2 in the even row, 0 in the odd one: row_const[0])
+                PairOps<NP>::dot(sr, evs, wq);
+                double sa, sb2;
+                pair_swap(sr, sa, sb2);
+                const double Sv = sa + sb2;
+                double Sinv = __builtin_amdgcn_rcp(Sv);
+                Sinv = fma(fma(-Sv, Sinv, 1.0), Sinv, Sinv);
+                Sinv = fma(fma(-Sv, Sinv, 1.0), Sinv, Sinv);
+                const double coef = ev * Sinv;
+                accq[0] = fma(ev, coef, accq[0]);
+                PairOps<NP>::rank1(colh, evs, -coef);
+                int ex;
+                P = frexp(P * Sv, &ex);
+                E += ex;
+                ++nv;
+                return;
+            }
             fetch_wq();
             double ev[CPL];
 #pragma unroll
@@ -759,7 +863,15 @@ __device__ __forceinline__ void logl_body(const KParams &p)
         // one frame t >= 1: predict (pyx:206-241), masked update (pyx:244-248)
         auto frame = [&](const double (&xv)[CPL], double probe) {
             if (ROW && kLean) s2_now = row_const[0];
-            if (MODE == kModal) {
+            if constexpr (PAIR) {
+#pragma unroll
+                for (int k = 0; k < NP / 2; ++k) colh[k] = fma(L.v[0][k], colh[k], sgd[k]);
+                if (HASG && isM[0]) {
+                    const double *__restrict__ gb = p.states + (size_t)s * SB + StateBlock::G(NP) + xoff[0] * NP + odd;
+#pragma unroll
+                    for (int k = 0; k < NP / 2; ++k) colh[k] += gb[2 * k];
+                }
+            } else if (MODE == kModal) {
 #pragma unroll
                 for (int q = 0; q < CPL; ++q)
 #pragma unroll
@@ -1065,7 +1177,9 @@ __device__ __forceinline__ void logl_body(const KParams &p)
             nrun = -1; // the run starts at frame 1
             fetch(xc, pc); // frame 0
             fetch(xn, pn); // frame 1 (or the first padding row)
+            pack();
             if (ALLVALID || !isnan(pc)) update(xc);
+            unpack();
         }
         // this launch builds the prefix table: the state after every frame goes to its record (tasks have K1 = 1, s is fixed)
         auto dump = [&](int tt) {
@@ -1256,6 +1370,7 @@ __device__ __forceinline__ void logl_body(const KParams &p)
                 return next_start < tc ? next_start : tc;
             };
             int t_event = next_event();
+            pack();
             while (t < T) {
                 // invariant: xn holds frame t, the pointers stand at frame t + 1.  The next frame's data are asked for FIRST, in
                 // front of the branch: in one basic block with the frame the scheduler sinks the load behind the last use of the
@@ -1265,11 +1380,13 @@ __device__ __forceinline__ void logl_body(const KParams &p)
                 pc = pn;
                 fetch(xn, pn);
                 if (t >= t_event) {
+                    unpack();
                     if (jumping && t == t_check) {
                         (void)compare_with_table();
                         if (t >= T) break;
                     }
                     if (t >= next_start) enter_segment(t);
+                    pack();
                     t_event = next_event();
                 }
                 frame(xc, pc);
@@ -1328,14 +1445,14 @@ __device__ __forceinline__ void logl_body(const KParams &p)
                     p.trans_dump[td->trans0 + (((int64_t)e * S + s_old) * S + ssv[1]) * T + t0] = en;
                 p.out[otask] = 0.0;
             }
-        } else if (gl == 0) {
+        } else if (lead) {
             p.out[otask] = extra;
         }
         // bench accounting: one of kFrameCounters words per workgroup slot (a single word would serialise ten thousand
         // atomics that all arrive at the end of a short launch)
-        if (p.frames_run && gl == 0) atomicAdd(p.frames_run + (blockIdx.x % kFrameCounters), (unsigned long long)nrun);
+        if (p.frames_run && lead) atomicAdd(p.frames_run + (blockIdx.x % kFrameCounters), (unsigned long long)nrun);
 #ifdef BILD_TASK_CLOCK
-        if (p.frames_task && gl == 0)
+        if (p.frames_task && lead)
 #if BILD_TASK_CLOCK == 3
             p.frames_task[otask] = (int32_t)(((((clock_a - clock_begin) / 2) & 0x3ff) << 20) | ((((clock_b - clock_begin) / 2) & 0x3ff) << 10) |
                                              (((clock_c - clock_begin) / 2) & 0x3ff));
@@ -1344,7 +1461,7 @@ __device__ __forceinline__ void logl_body(const KParams &p)
             p.frames_task[otask] = BILD_TASK_CLOCK == 2 ? (int32_t)(((clock_events & 0xffffull) << 16) | (unsigned)n_events)
                                                         : (int32_t)(((clock_begin & 0xffffull) << 16) | (wall_clock64() & 0xffffull));
 #else
-        if (p.frames_task && gl == 0) p.frames_task[otask] = nrun;
+        if (p.frames_task && lead) p.frames_task[otask] = nrun;
 #endif
         wave_lds_fence();
     }
@@ -1353,6 +1470,20 @@ __device__ __forceinline__ void logl_body(const KParams &p)
 template <int NP, int CPL, int G, int W, int OCC, int LAY, int MODE, int FLAVOR, bool DUMP = false, bool JUMP = false, bool BUILD = false>
 __global__ void __launch_bounds__(64 * W, OCC) logl_kernel(const KParams p)
 {
+    // The listed frame loop (geometry 23) takes the two-row frame whenever no wave has to carry more than two tasks: the list fits
+    // the grid's row pairs once.  A task alone on its wave -- the chains that end the launch -- then issues ~45 instead of ~61 vector
+    // instructions per frame (10k x k = 4: step 51.9-52.2 -> 48.3 us); longer lists (throughput-bound: four tasks per wave share one
+    // instruction stream) keep the one-row frame.  The length is known only here, behind the walk; both frames give the same bits.
+    if constexpr (LAY == 3 && MODE == kModal && JUMP && !DUMP && !BUILD) {
+        if (p.work != nullptr) {
+            int64_t tot = 0;
+            for (int bq = 0; bq < kWorkBuckets; ++bq) tot += p.work_counts[bq];
+            if (tot <= (int64_t)gridDim.x * W * (64 / G / 2)) {
+                logl_body<NP, CPL, G, W, OCC, LAY, MODE, FLAVOR, DUMP, JUMP, BUILD, true>(p);
+                return;
+            }
+        }
+    }
     logl_body<NP, CPL, G, W, OCC, LAY, MODE, FLAVOR, DUMP, JUMP, BUILD>(p);
 }
 
