@@ -141,6 +141,8 @@ _SIGNATURES = {
     # Rouse trajectory generator (sim.cpp)
     'bild_rouse_simulate': (ctypes.c_int, [ctypes.c_int] * 3 + [_dp] * 7 + [ctypes.c_int, _ip, ctypes.c_int, _ip, _ip, _vp, _dp, _dp,
                                            ctypes.c_uint64, ctypes.c_int64, _dp]),
+    # GenericGaussianModel trajectory generator (gauss_sim.cpp)
+    'bild_gauss_simulate': (ctypes.c_int, [_vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip, _vp, _dp, ctypes.c_uint64, ctypes.c_int64, _dp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -319,6 +321,7 @@ class GaussModelHandle:
         S, d, L1 = msd.shape
         assert order.shape == (S, d) and mean.shape == (S, d) and msd_inf.shape == (S, d)
         self.S, self.d, self.Tmax = S, d, L1 - 1
+        self.order = order
         self._h = _vp()
         check(lib().bild_gauss_model_create(S, d, L1 - 1, iptr(order), dptr(mean), dptr(msd), dptr(msd_inf), ctypes.byref(self._h)))
 
@@ -408,6 +411,34 @@ def rouse_simulate(V, b, sqrt_sig, sqrt_cinf, VtG, VtM0, w, T, seg_start, seg_st
                                     n, iptr(T), K1, iptr(seg_start), iptr(seg_state), None if miss is None else aptr(miss),
                                     dptr(err), None if z is None else dptr(z), int(seed), int(scratch_bytes),
                                     dptr(out) if rows else None))
+    return out
+
+
+def gauss_simulate(model, T, seg_start, seg_state, missing, normals=None, seed=0, scratch_bytes=0):
+    """
+    GenericGaussianModel trajectories (bild_gauss_simulate) of the model handle ``model``: per trajectory T (n,), segments
+    (n, K1), missing (sum T,) bool or None; normals: every trajectory's normals in the loop's order, one trajectory after
+    the other (replay), or None (device mode, keyed by ``seed``).  ``scratch_bytes`` bounds the chunks of normals (0: the
+    library's rule).  A covariance that is not positive definite raises numpy.linalg.LinAlgError.  -> (sum T, d) float64
+    """
+    T, seg_start, seg_state = i32(T), i32(seg_start), i32(seg_state)
+    n = T.shape[0]
+    K1 = seg_start.shape[1] if seg_start.ndim == 2 else 1
+    assert seg_start.shape == seg_state.shape == (n, K1)
+    rows = int(T.sum())
+    miss = None if missing is None else np.ascontiguousarray(missing, dtype=np.uint8)
+    assert miss is None or miss.shape == (rows,)
+    z = None if normals is None else f64(normals)
+    assert z is None or (seg_state.min(initial=0) >= 0 and seg_state.max(initial=0) < model.S and
+                         z.shape == (rows * model.d - int(model.order[seg_state[:, 0]].sum()),))
+    out = np.empty((rows, model.d), dtype=np.float64)
+    code = lib().bild_gauss_simulate(model._h, n, iptr(T), K1, iptr(seg_start), iptr(seg_state), None if miss is None else aptr(miss),
+                                     None if z is None else dptr(z), int(seed), int(scratch_bytes), dptr(out) if rows else None)
+    if code == ERR_INVALID:
+        msg = lib().bild_last_error().decode()
+        if 'not positive definite' in msg:
+            raise np.linalg.LinAlgError(msg)
+    check(code)
     return out
 
 

@@ -47,6 +47,10 @@ int launch_gauss_factor(const GaussJobSet &, const GaussJob *, int, double *, in
 int launch_gauss_solve(const GaussJobSet &, const GaussJob *, int, int, void *) { return 1; }
 int launch_gauss_accumulate(const GaussAccum &, void *) { return 1; }
 int launch_gauss_walk(const GaussWalk &, bool, void *) { return 1; }
+int launch_gauss_factor_sets(const GaussJobSet *, const GaussJob *, int, void *) { return 1; }
+int launch_gauss_sim_normals(const GaussSimProduct &, void *) { return 1; }
+int launch_gauss_sim_product(const GaussSimProduct &, void *) { return 1; }
+int launch_gauss_sim_assemble(const GaussSimAssemble &, void *) { return 1; }
 } // namespace bild
 #include "exchange.h"
 namespace bild {

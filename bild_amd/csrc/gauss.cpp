@@ -6,13 +6,6 @@
 #include "likelihood.h"
 #include "gauss.h"
 
-struct bild_gauss_model {
-    int S = 0, d = 0, L = 0;            // L: the largest lag of the MSD tables
-    std::vector<int32_t> order;         // S x d
-    std::vector<double> mean, msd_inf;  // S x d
-    std::vector<double> msd;            // S x d x (L + 1)
-};
-
 struct bild_gauss_trajset {
     const bild_gauss_model *model = nullptr;
     int n_traj = 0;
@@ -285,6 +278,7 @@ int bild_gauss_model_create(int S, int d, int Tmax, const int32_t *ss_order, con
 
 int bild_gauss_model_destroy(bild_gauss_model *m)
 {
+    if (m && m->factors) (void)hipFree(m->factors);     // only a model that simulated holds device memory
     delete m;
     return BILD_OK;
 }

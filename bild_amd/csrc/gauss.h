@@ -1,7 +1,25 @@
-// What gauss.cpp (host) and gauss.hip (kernels) share: GenericGaussianModel's table layout, the kernels' parameter
-// blocks and their launchers.  Private to the library.
+// What gauss.cpp, gauss_sim.cpp (host) and gauss.hip (kernels) share: the model handle, GenericGaussianModel's table
+// layout, the kernels' parameter blocks and their launchers.  Private to the library.
 #pragma once
 #include <stdint.h>
+
+#include <mutex>
+#include <vector>
+
+struct bild_gauss_model {
+    int S = 0, d = 0, L = 0;            // L: the largest lag of the MSD tables
+    std::vector<int32_t> order;         // S x d
+    std::vector<double> mean, msd_inf;  // S x d
+    std::vector<double> msd;            // S x d x (L + 1)
+    // the generator's Toeplitz factors (gauss_sim.cpp): device memory from the first bild_gauss_simulate on, grown with
+    // the longest trajectory; freed by bild_gauss_model_destroy.  A model that never simulates holds host memory only.
+    mutable std::mutex sim_mu;
+    mutable double *factors = nullptr;
+    mutable int factor_T = 0;                   // frames the factors cover (0: none yet)
+    mutable std::vector<int64_t> factor_off;    // S x d: offset of the factor of (state, dimension)
+    mutable std::vector<int> factor_n;          // S x d: its order (= leading dimension): factor_T, or factor_T - 1 (ss_order 1)
+    mutable std::vector<int> factor_ok;         // S x d: leading pivots that are finite and positive
+};
 
 namespace bild {
 
@@ -61,6 +79,59 @@ struct GaussWalk {
     int64_t n;
     int K1, S;
 };
+
+// The generator (gauss_sim.cpp; kernels in gauss.hip).  Column: one (trajectory, interval, dimension) against the leading
+// len x len block of its (state, dimension) factor: y_r = sum_{j <= r} L_rj zvec_j, zvec_j = z[z + j] for j >= skip0 and
+// 0 below; y_r (r >= skip0) goes to out row `row + r`.
+struct GaussSimCol {
+    int64_t z;          // zvec_j = Z[z + j] (j >= skip0)
+    int64_t row;        // output row (of d values) of entry 0: the frame frame0 of the trajectory
+    int len, skip0;     // rows of the factor used; skip0 = 1: a later ss_order-0 interval (entry 0 is the conditioning slot)
+    int frame0, traj;   // device mode: the normal of entry j is that of (trajectory traj of the call, frame frame0 + j)
+    int k, pad;
+};
+
+// up to kGaussSimTN columns of one (state, dimension), longest first
+struct GaussSimBlock {
+    const double *L;    // the factor (column-major, leading dimension ld)
+    int ld, k, c0, nc, nmax;
+};
+
+struct GaussSimTask {
+    int block, r0;      // row tile [r0, r0 + kGaussSimTM)
+};
+
+constexpr int kGaussSimTM = 64, kGaussSimTN = 32;
+
+struct GaussSimProduct {
+    const GaussSimCol *cols;
+    const GaussSimBlock *blocks;
+    const GaussSimTask *tasks;
+    double *z;          // the normals of the chunk (device mode: written by gauss_sim_normals_kernel)
+    double *out;
+    int ntasks, ncols, d;
+    uint64_t seed;
+};
+
+// the sequential pass: one workgroup per (trajectory, group of kGaussSimDG dimensions)
+constexpr int kGaussSimDG = 8;
+
+struct GaussSimAssemble {
+    const int64_t *frame_off;   // first output row of each trajectory
+    const int64_t *iv_off;      // per trajectory: its first interval in iv (n + 1 entries)
+    const int32_t *iv;          // intervals (t0, t1, state), runs of equal state
+    const int32_t *order;       // S x d
+    const double *mean;         // S x d
+    const double *const *L;     // S x d: the factors (column 0 is the conditioning column)
+    const uint8_t *missing;     // per output row
+    double *out;
+    int n, d;
+};
+
+int launch_gauss_factor_sets(const GaussJobSet *d_sets, const GaussJob *d_jobs, int nsets, void *stream);
+int launch_gauss_sim_normals(const GaussSimProduct &p, void *stream);
+int launch_gauss_sim_product(const GaussSimProduct &p, void *stream);
+int launch_gauss_sim_assemble(const GaussSimAssemble &p, void *stream);
 
 int launch_gauss_factor(const GaussJobSet &p, const GaussJob *d_jobs, int njobs, double *scratch, int64_t slot_doubles, void *stream);
 int launch_gauss_solve(const GaussJobSet &p, const GaussJob *d_jobs, int njobs, int ld0, void *stream);

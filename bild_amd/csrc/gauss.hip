@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "gauss.h"
+#include "philox.h"
 
 namespace bild {
 namespace {
@@ -51,15 +52,13 @@ __device__ __forceinline__ double gauss_rhs(const GaussJobSet &p, int rank, bool
     return (xv[j + 1] - xv[j]) - p.mean;
 }
 
-__global__ void __launch_bounds__(kThreads) gauss_factor_kernel(GaussJobSet p, const GaussJob *__restrict__ jobs, double *__restrict__ scratch,
-                                                                 int64_t slot_doubles)
+// The left-looking column sweep of one job by one workgroup (the likelihood's factorisations and the generator's factors)
+__device__ __forceinline__ void gauss_factor_job(const GaussJobSet &p, const GaussJob &job, double *__restrict__ L)
 {
     __shared__ double diag;
-    const GaussJob job = jobs[blockIdx.x];
     const int n = job.n;
     const int rows = job.tau_row >= 0 ? n + 1 : n;      // with the data row, or (the shared factor) without
     const int ld = rows;
-    double *__restrict__ L = job.factor_out ? p.factor : scratch + (int64_t)blockIdx.x * slot_doubles;
     const int32_t *__restrict__ u = p.vidx + job.rank;
     double *__restrict__ tau = job.tau_row >= 0 ? p.tau + (int64_t)job.tau_row * p.tau_ld : nullptr;
 
@@ -83,6 +82,21 @@ __global__ void __launch_bounds__(kThreads) gauss_factor_kernel(GaussJobSet p, c
         if (threadIdx.x == 0) colj[j] = djj;
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(kThreads) gauss_factor_kernel(GaussJobSet p, const GaussJob *__restrict__ jobs, double *__restrict__ scratch,
+                                                                 int64_t slot_doubles)
+{
+    const GaussJob job = jobs[blockIdx.x];
+    gauss_factor_job(p, job, job.factor_out ? p.factor : scratch + (int64_t)blockIdx.x * slot_doubles);
+}
+
+// one job per set, each written to its set's factor (the generator's S x d Toeplitz factors in one launch)
+__global__ void __launch_bounds__(kThreads) gauss_factor_sets_kernel(const GaussJobSet *__restrict__ sets, const GaussJob *__restrict__ jobs)
+{
+    const GaussJobSet p = sets[blockIdx.x];
+    const GaussJob job = jobs[blockIdx.x];
+    gauss_factor_job(p, job, p.factor);
 }
 
 __global__ void __launch_bounds__(kThreads) gauss_solve_kernel(GaussJobSet p, const GaussJob *__restrict__ jobs, int ld0)
@@ -205,7 +219,186 @@ __global__ void __launch_bounds__(kThreads) gauss_walk_kernel(GaussWalk p)
     p.out[r] = acc;
 }
 
+
+// ---------------------------------------------------------------- the generator (bild_gauss_simulate, gauss_sim.cpp)
+// Per (state, dimension) one lower Cholesky factor L of the Toeplitz covariance of the longest window (gauss_factor_sets_kernel);
+// a column (trajectory, interval, dimension) is the product of its leading block with the interval's normals, and a
+// sequential pass per trajectory adds the means, the conditioning column and the ss_order-1 prefix sums.  DESIGN.md
+// section 12.
+
+// Device mode: the normal of (trajectory i of the call, frame t, dimension k) is one of the Box-Muller pair of the
+// Philox-4x32-10 block with key = seed, counter (i, t / 2, k, 1): even t the cosine, odd t the sine.  Written to Z in the
+// replay layout (column after column), so that the product reads both modes alike.  One wave per column.
+__global__ void __launch_bounds__(64) gauss_sim_normals_kernel(GaussSimProduct p)
+{
+    const GaussSimCol c = p.cols[blockIdx.x];
+    const int f_lo = c.frame0 + c.skip0, f_hi = c.frame0 + c.len;     // frames [f_lo, f_hi)
+    for (int q = (f_lo >> 1) + (int)threadIdx.x; 2 * q < f_hi; q += 64) {
+        uint32_t r[4];
+        philox4x32_10((uint32_t)c.traj, (uint32_t)q, (uint32_t)c.k, 1u, (uint32_t)p.seed, (uint32_t)(p.seed >> 32), r);
+        double n0, n1;
+        philox_normal_pair(r, &n0, &n1);
+        const int t = 2 * q;
+        if (t >= f_lo) p.z[c.z + (t - c.frame0)] = n0;
+        if (t + 1 >= f_lo && t + 1 < f_hi) p.z[c.z + (t + 1 - c.frame0)] = n1;
+    }
+}
+
+// One workgroup per task: a tile of kGaussSimTM rows x the block's columns.  Lane (tx, ty): row r0 + tx, columns
+// 8 ty .. 8 ty + 7.  The factor tile (j <= row only; zeros above the diagonal, whose memory is never written) and the
+// normals tile go through LDS, kGaussSimKC entries of j at a time; every output sums over j in ascending order, so a
+// column's values do not depend on its block, its tile or the batch.
+constexpr int kGaussSimKC = 32;
+constexpr int kGaussSimCPL = kGaussSimTN / (kThreads / kGaussSimTM);     // columns per lane (8)
+
+__global__ void __launch_bounds__(kThreads) gauss_sim_product_kernel(GaussSimProduct p)
+{
+    __shared__ double Ls[kGaussSimKC][kGaussSimTM];
+    __shared__ double Zs[kGaussSimKC][kGaussSimTN];
+    __shared__ GaussSimCol cs[kGaussSimTN];
+    const GaussSimTask task = p.tasks[blockIdx.x];
+    const GaussSimBlock b = p.blocks[task.block];
+    const int tid = threadIdx.x, tx = tid % kGaussSimTM, ty = tid / kGaussSimTM;
+    const int r0 = task.r0, r = r0 + tx;
+    if (tid < b.nc) cs[tid] = p.cols[b.c0 + tid];
+    __syncthreads();
+
+    double acc[kGaussSimCPL];
+#pragma unroll
+    for (int q = 0; q < kGaussSimCPL; ++q) acc[q] = 0.0;
+    const int jend = min(r0 + kGaussSimTM, b.nmax);
+    const double *__restrict__ L = b.L;
+    for (int j0 = 0; j0 < jend; j0 += kGaussSimKC) {
+        for (int e = tid; e < kGaussSimKC * kGaussSimTM; e += kThreads) {
+            const int jj = e / kGaussSimTM, ii = e % kGaussSimTM, j = j0 + jj, rr = r0 + ii;
+            Ls[jj][ii] = (j <= rr && rr < b.nmax) ? L[(int64_t)j * b.ld + rr] : 0.0;
+        }
+        for (int e = tid; e < kGaussSimKC * kGaussSimTN; e += kThreads) {
+            const int jj = e / kGaussSimTN, cc = e % kGaussSimTN, j = j0 + jj;
+            double v = 0.0;
+            if (cc < b.nc) {
+                const GaussSimCol &c = cs[cc];
+                if (j >= c.skip0 && j < c.len) v = p.z[c.z + j];
+            }
+            Zs[jj][cc] = v;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int jj = 0; jj < kGaussSimKC; ++jj) {
+            const double a = Ls[jj][tx];
+#pragma unroll
+            for (int q = 0; q < kGaussSimCPL; ++q) acc[q] = fma(a, Zs[jj][ty * kGaussSimCPL + q], acc[q]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < kGaussSimCPL; ++q) {
+        const int cc = ty * kGaussSimCPL + q;
+        if (cc >= b.nc) break;
+        const GaussSimCol &c = cs[cc];
+        if (r >= c.skip0 && r < c.len) p.out[(c.row + r) * p.d + b.k] = acc[q];
+    }
+}
+
+// inclusive prefix sum over the workgroup (kThreads lanes); every lane calls it
+__device__ __forceinline__ double gauss_block_scan(double v, double *wsum)
+{
+    const int lane = threadIdx.x % warpSize, w = threadIdx.x / warpSize;
+    for (int o = 1; o < warpSize; o *= 2) {
+        const double u = __shfl_up(v, o);
+        if (lane >= o) v += u;
+    }
+    if (lane == warpSize - 1) wsum[w] = v;
+    __syncthreads();
+    double before = 0.0;
+    for (int q = 0; q < w; ++q) before += wsum[q];
+    __syncthreads();
+    return before + v;
+}
+
+// One workgroup per (trajectory, group of kGaussSimDG dimensions), lanes over frames, the intervals in order, kThreads
+// frames at a time.  out holds the product y (entry 0 of an ss_order-1 first interval has none); per dimension:
+//   ss_order 0, first interval:  x_t = m + y_t
+//   ss_order 0, later interval:  x_t = m + y_t + a L[t - t0 + 1, 0],  a = (x_{t0-1} - m) / L[0, 0]
+//   ss_order 1:                  x_t = x_{t0-1} + sum_{t0 <= u <= t} (y_u + m)   (first interval: x_0 = 0, the sum from 1)
+// The frames of a pass are staged in LDS and written as whole rows of the group, NaN where missing.
+__global__ void __launch_bounds__(kThreads) gauss_sim_assemble_kernel(GaussSimAssemble p)
+{
+    __shared__ double buf[kThreads * kGaussSimDG];
+    __shared__ double carry[kGaussSimDG], start[kGaussSimDG], wsum[kThreads / 64];
+    const int i = blockIdx.x, d = p.d;
+    const int k0 = blockIdx.y * kGaussSimDG, dd = min(kGaussSimDG, d - k0);
+    const int tid = threadIdx.x;
+    const int64_t row0 = p.frame_off[i];
+    double *__restrict__ out = p.out;
+    if (tid < kGaussSimDG) carry[tid] = 0.0;
+    __syncthreads();
+    for (int v = p.iv_off[i]; v < p.iv_off[i + 1]; ++v) {
+        const int t0 = p.iv[3 * v], t1 = p.iv[3 * v + 1], s = p.iv[3 * v + 2];
+        if (tid < kGaussSimDG) start[tid] = carry[tid];     // x_{t0-1} (0 before the first interval)
+        __syncthreads();
+        for (int c0 = t0; c0 < t1; c0 += kThreads) {
+            const int nf = min(kThreads, t1 - c0), t = c0 + tid;
+            const bool in = tid < nf;
+            for (int kk = 0; kk < dd; ++kk) {
+                const int k = k0 + kk, sk = s * d + k;
+                const double m = p.mean[sk];
+                const double y = in && !(t == 0 && p.order[sk] == 1) ? out[(row0 + t) * d + k] : 0.0;
+                double x;
+                if (p.order[sk] == 0) {
+                    x = m + y;
+                    if (t0 > 0 && in) {
+                        const double *__restrict__ L = p.L[sk];
+                        x = fma((start[kk] - m) / L[0], L[t - t0 + 1], x);
+                    }
+                } else {
+                    const double base = carry[kk];
+                    x = base + gauss_block_scan(in && t > 0 ? y + m : 0.0, wsum);
+                }
+                if (in) buf[tid * kGaussSimDG + kk] = x;
+                if (tid == nf - 1) carry[kk] = x;
+                __syncthreads();
+            }
+            for (int e = tid; e < nf * dd; e += kThreads) {
+                const int f = e / dd, kk = e - f * dd;
+                const int64_t rr = row0 + c0 + f;
+                out[rr * d + k0 + kk] = p.missing[rr] ? __longlong_as_double(0x7ff8000000000000ll) : buf[f * kGaussSimDG + kk];
+            }
+            __syncthreads();
+        }
+    }
+}
+
 } // namespace
+
+int launch_gauss_factor_sets(const GaussJobSet *d_sets, const GaussJob *d_jobs, int nsets, void *stream)
+{
+    if (nsets <= 0) return 0;
+    hipLaunchKernelGGL(gauss_factor_sets_kernel, dim3(nsets), dim3(kThreads), 0, (hipStream_t)stream, d_sets, d_jobs);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int launch_gauss_sim_normals(const GaussSimProduct &p, void *stream)
+{
+    if (p.ncols <= 0) return 0;
+    hipLaunchKernelGGL(gauss_sim_normals_kernel, dim3(p.ncols), dim3(64), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int launch_gauss_sim_product(const GaussSimProduct &p, void *stream)
+{
+    if (p.ntasks <= 0) return 0;
+    hipLaunchKernelGGL(gauss_sim_product_kernel, dim3(p.ntasks), dim3(kThreads), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int launch_gauss_sim_assemble(const GaussSimAssemble &p, void *stream)
+{
+    if (p.n <= 0) return 0;
+    const dim3 grid((unsigned)p.n, (unsigned)((p.d + kGaussSimDG - 1) / kGaussSimDG));
+    hipLaunchKernelGGL(gauss_sim_assemble_kernel, grid, dim3(kThreads), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
 
 int launch_gauss_factor(const GaussJobSet &p, const GaussJob *d_jobs, int njobs, double *scratch, int64_t slot_doubles, void *stream)
 {

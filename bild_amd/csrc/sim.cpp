@@ -1,39 +1,11 @@
 // The Rouse trajectory generator: the C ABI bild_rouse_simulate (include/bild_amd.h), its checks, the staging of the
 // per-state modal arrays and of the trajectories, and the chunked upload of host-drawn normals.  Kernel: sim.hip.
-#include "likelihood.h"
 #include "sim.h"
+#include "sim_host.h"
 
 namespace {
 
 using namespace bild;
-
-// device memory of one call, freed on every path
-struct SimBufs {
-    std::vector<void *> ptrs;
-    hipStream_t stream = nullptr;
-    ~SimBufs()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (void *p : ptrs) (void)hipFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    template <class X> int put(X **out, const void *host, size_t count)
-    {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(X));
-        if (e != hipSuccess) return fail(BILD_ERR_NOMEM, "hipMalloc(%zu) failed: %s", count * sizeof(X), hipGetErrorString(e));
-        ptrs.push_back(p);
-        *out = static_cast<X *>(p);
-        if (host && count) HIP_TRY(hipMemcpyAsync(p, host, count * sizeof(X), hipMemcpyHostToDevice, stream));
-        return BILD_OK;
-    }
-};
-
-#define SIM_TRY(x)                      \
-    do {                                \
-        int rc_ = (x);                  \
-        if (rc_ != BILD_OK) return rc_; \
-    } while (0)
 
 bool all_finite(const double *a, size_t n)
 {
@@ -93,7 +65,7 @@ extern "C" int bild_rouse_simulate(int S, int N, int d, const double *V, const d
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     // replay scratch: at most 1 GiB and a third of the free memory (or the caller's budget), whole trajectories per chunk
-    const int64_t scratch = scratch_bytes > 0 ? scratch_bytes : std::min<int64_t>(1ll << 30, (int64_t)(free_b / 3));
+    const int64_t scratch = sim_scratch_bytes(scratch_bytes, free_b);
     const int64_t scratch_doubles = std::min<int64_t>(scratch / 8, z_off[n]);
     if (normals)
         for (int i = 0; i < n; ++i)
@@ -162,8 +134,7 @@ extern "C" int bild_rouse_simulate(int S, int N, int d, const double *V, const d
         SIM_TRY(bufs.put(&p.z_off, z_off.data(), n));
         p.z = d_z;
         for (int first = 0; first < n;) {
-            int last = first + 1;
-            while (last < n && z_off[last + 1] - z_off[first] <= scratch_doubles) ++last;
+            const int last = sim_chunk_end(z_off, first, n, scratch_doubles);
             // (pageable source: the copy is staged, and the next chunk's copy waits for this chunk's kernel on the stream)
             HIP_TRY(hipMemcpyAsync(d_z, normals + z_off[first], (size_t)(z_off[last] - z_off[first]) * 8, hipMemcpyHostToDevice,
                                    bufs.stream));

@@ -12,7 +12,8 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .models import MultiStateModel, MultiStateRouse
+from .models import (MultiStateModel, MultiStateRouse, _REPLAY_GROUP_BYTES, _draw_normals, _missing_frames, _missing_is_none,
+                     _ragged_segments)
 from .profiles import segments_from_states
 from .trajectory import Trajectory
 
@@ -261,3 +262,92 @@ class GenericGaussianModel(MultiStateModel):
         data = np.concatenate([np.array(snip).T for snip in snippets])
         data[missing] = np.nan
         return Trajectory(data, loopingprofile=profile)
+
+    def trajectories_from_loopingprofiles(self, profiles, missing_frames=None, rng=None, seed=None):
+        """
+        Many trajectories at once, generated on the GPU: one Cholesky factor per (state, dimension)
+        serves every interval, so a trajectory costs one triangular product per interval and dimension.
+
+        profiles : sequence of `Loopingprofile` or 1-d integer arrays (lengths may differ), or an (n, T) integer array;
+            at most `max_T` frames each
+        missing_frames : one of `trajectory_from_loopingprofile`'s forms (None, a fraction, a count, an index array -- as
+            a NumPy array), applied to every trajectory, or a list / tuple with one such entry per trajectory
+        rng : numpy Generator -- replay mode: the host draws exactly the numbers that
+            ``[self.trajectory_from_loopingprofile(p, missing_frames, rng=rng) for p in profiles]`` draws, in the same
+            order, and leaves ``rng`` where that loop would; the results equal the loop's to rounding.
+        seed : int in [0, 2**64) -- device mode (also when neither ``rng`` nor ``seed`` is given, with a fresh seed): the
+            normals come from a counter-based generator on the device; trajectory ``i`` is a pure function of
+            (seed, i, its profile, its missing frames), and its missing frames are drawn from
+            ``np.random.default_rng([seed, i])``.
+
+        The model keeps its factors on the device after the first call (and rebuilds them, once, for a longer
+        trajectory).  A covariance that is not positive definite raises numpy.linalg.LinAlgError, as the loop does.
+
+        Returns
+        -------
+        list of `Trajectory`, one per profile and in order
+        """
+        if rng is not None and seed is not None:
+            raise ValueError("give either rng (replay mode) or seed (device mode), not both")
+        items = list(profiles)
+        states = [np.asarray(p[:]) for p in items]
+        S = self.nStates
+        for i, st in enumerate(states):
+            if st.ndim != 1 or len(st) < 1 or not np.issubdtype(st.dtype, np.integer):
+                raise ValueError(f"profile {i} is not a non-empty 1-d integer array")
+            if st.min() < 0 or st.max() >= S:
+                raise ValueError(f"profile {i} has a state outside 0 .. {S - 1}")
+            if len(st) > self.max_T:
+                raise ValueError(f"profile {i} has {len(st)} frames: GenericGaussianModel generates at most {self.max_T} "
+                                 f"(the GPU takes up to {MAX_T} frames, the MSD tables cover {self.msd.shape[2]} lags)")
+        n = len(states)
+        if isinstance(missing_frames, (list, tuple)):
+            if len(missing_frames) != n:
+                raise ValueError(f"missing_frames has {len(missing_frames)} entries for {n} profiles")
+            specs = list(missing_frames)
+        else:
+            specs = [missing_frames] * n
+        if seed is not None:
+            seed = int(seed)
+            if not 0 <= seed < 2 ** 64:
+                raise ValueError("seed must be an integer in [0, 2**64)")
+        if n == 0:
+            return []
+
+        T = np.array([len(st) for st in states], dtype=np.int64)
+        seg_start, seg_state = _ragged_segments(states, T)
+        d = self.d
+        offs = np.concatenate([[0], np.cumsum(T)])
+
+        if rng is None:     # device mode
+            mask = np.zeros(int(offs[-1]), dtype=bool)
+            if seed is None:
+                seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+            for i, spec in enumerate(specs):
+                if not _missing_is_none(spec):
+                    drawn = np.isscalar(spec)
+                    mask[offs[i]:offs[i + 1]][_missing_frames(spec, int(T[i]), np.random.default_rng([seed, i]) if drawn else None)] = True
+            data = _lib.gauss_simulate(self.handle(), T, seg_start, seg_state, mask, seed=seed)
+        else:               # replay mode: host groups of at most _REPLAY_GROUP_BYTES of normals
+            per = normals_per_trajectory(self.ss_order, seg_state[:, 0], T)
+            data = np.empty((int(offs[-1]), d))
+            i0 = 0
+            while i0 < n:
+                i1 = i0 + 1
+                while i1 < n and per[i0:i1 + 1].sum() * 8 <= _REPLAY_GROUP_BYTES:
+                    i1 += 1
+                mask, z = _draw_normals(specs[i0:i1], T[i0:i1], per[i0:i1], rng)
+                data[offs[i0]:offs[i1]] = _lib.gauss_simulate(self.handle(), T[i0:i1], seg_start[i0:i1], seg_state[i0:i1], mask,
+                                                              normals=z)
+                i0 = i1
+        return [Trajectory(data[offs[i]:offs[i + 1]], loopingprofile=items[i]) for i in range(n)]
+
+
+def normals_per_trajectory(ss_order, first_state, T):
+    """
+    How many normals `GenericGaussianModel.trajectory_from_loopingprofile` draws for a trajectory of T frames whose first
+    state is ``first_state``: per dimension T, one fewer where that state has ss_order 1 (its first frame is 0).
+    Vectorised over trajectories.
+    """
+    ss_order = np.asarray(ss_order)
+    return np.asarray(T, dtype=np.int64) * ss_order.shape[1] - ss_order[np.asarray(first_state)].sum(axis=1)

@@ -467,8 +467,16 @@ def _replay_draws(specs, T, N, d, rng):
     noise.  -> (missing mask (sum T,) bool, normals (sum T (N + 1) d,)), as bild_rouse_simulate takes them
     """
     T = np.asarray(T, dtype=np.int64)
+    return _draw_normals(specs, T, T * (N + 1) * d, rng)
+
+
+def _draw_normals(specs, T, per, rng):
+    """
+    Per trajectory of length T[i]: its missing frames drawn from ``rng`` as the loops draw them, then one
+    ``standard_normal`` fill of per[i] normals.  -> (missing mask (sum T,) bool, normals (sum per,)) in that order
+    """
+    T, per = np.asarray(T, dtype=np.int64), np.asarray(per, dtype=np.int64)
     offs = np.concatenate([[0], np.cumsum(T)])
-    per = T * (N + 1) * d
     mask = np.zeros(int(offs[-1]), dtype=bool)
     z = np.empty(int(per.sum()))
     zo = 0

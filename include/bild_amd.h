@@ -614,6 +614,35 @@ int bild_gauss_logl_segments(const bild_gauss_model *m, const bild_gauss_trajset
 int bild_gauss_logl_st(const bild_gauss_model *m, const bild_gauss_trajset *ts, int64_t n, int K1, const double *ss,
                        const int64_t *thetas, const int32_t *traj_id, double *out);
 
+/* n trajectories of the model (GenericGaussianModel.trajectories_from_loopingprofiles), the batched form of the loop of
+ * GenericGaussianModel.trajectory_from_loopingprofile.  Trajectory i has 1 <= T[i] <= 2048 frames, at most the model's
+ * Tmax + 1 (else BILD_ERR_UNSUPPORTED), and the profile given by its segments (n x K1, as bild_gauss_logl_segments takes
+ * them; starts >= T[i] pad); its intervals are the runs of equal state.  missing (sum T bytes, may be NULL) marks frames to
+ * return as NaN (every dimension).  out receives the sum T x d values, trajectory after trajectory, row-major.
+ *
+ * Per (state, dimension) one lower Cholesky factor of the Toeplitz covariance of the longest window serves every
+ * interval.  The model keeps these factors in device memory from its first call on and rebuilds
+ * them when a longer trajectory arrives (the first call, and each growth, pays the factorisations); results do not
+ * depend on that history.  Calls on one model are serialised.  A factor whose leading block of the size a column needs
+ * has a pivot that is not finite and positive: BILD_ERR_INVALID, naming the state, the dimension and the size.
+ *
+ * normals != NULL (replay): per trajectory, one after the other, the normals in the order the loop draws them:
+ * interval after interval, and within an interval dimension after dimension, for dimension k of the interval [t0, t1)
+ * in state s
+ *   first interval (t0 = 0):  t1 normals if ss_order[s][k] = 0, t1 - 1 if it is 1;
+ *   later intervals:          t1 - t0 normals;
+ * so sum_k (T[i] - ss_order[first state][k]) per trajectory.  They are uploaded in chunks of whole trajectories within
+ * scratch_bytes, or, when that is 0, within min(1 GiB, a third of the free device memory); a trajectory that alone
+ * exceeds the budget: BILD_ERR_UNSUPPORTED (in device mode as well, where the chunks are drawn on the device).
+ * normals == NULL (device mode): the normal of (index i of the trajectory in the call, frame t, dimension k) -- the one
+ * the loop would draw for frame t (for frame t + 1 ... : entry j of a first ss_order-1 interval belongs to frame j + 1,
+ * every other entry j of interval [t0, t1) to frame t0 + j) -- is one of the Box-Muller pair of the Philox-4x32-10 block
+ * with key = seed and counter (i, t / 2, k, 1), the cosine for even t, the sine for odd t (gauss.hip).  So trajectory i
+ * does not depend on the other trajectories of the call.  Synchronous. */
+int bild_gauss_simulate(const bild_gauss_model *m, int n, const int32_t *T, int K1, const int32_t *seg_start,
+                        const int32_t *seg_state, const uint8_t *missing, const double *normals, uint64_t seed,
+                        int64_t scratch_bytes, double *out);
+
 /* ---------------------------------------------------------------- Rouse trajectory generator -------
  * n trajectories of the multi-state Rouse model (MultiStateRouse.trajectories_from_loopingprofiles), computed in each
  * state's modal coordinates: per state s an orthonormal eigenbasis V[s] (N x N, row = monomer, column = mode) with
