@@ -143,6 +143,9 @@ _SIGNATURES = {
                                            ctypes.c_uint64, ctypes.c_int64, _dp]),
     # GenericGaussianModel trajectory generator (gauss_sim.cpp)
     'bild_gauss_simulate': (ctypes.c_int, [_vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip, _vp, _dp, ctypes.c_uint64, ctypes.c_int64, _dp]),
+    # Kalman filter and smoother (kalman.cpp)
+    'bild_kalman_segments': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, _vp, ctypes.c_int64]),
+    'bild_kalman_mixture': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, _dp, _dp, _dp, ctypes.c_int64]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -538,6 +541,52 @@ def frames_executed_fraction(model, ts, seg_start, traj_id=None, order=None, pat
     check(lib().bild_frames_executed(model._h, ts._h, n, K1, iptr(seg_start), iptr(tid), iptr(od), _flags(path, prefix=prefix),
                                      ctypes.byref(tot), ctypes.byref(run)))
     return run.value / tot.value if tot.value else 1.0
+
+
+KALMAN_OUTPUTS = ('terms', 'pred_mean', 'pred_var', 'filt_mean', 'filt_var', 'smooth_mean', 'smooth_var', 'innov')
+
+
+class KalmanOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in KALMAN_OUTPUTS] + [('T_max', ctypes.c_int32)]
+
+
+def kalman_segments(model, ts, seg_start, seg_state, traj_id=None, outputs=KALMAN_OUTPUTS, T_max=None, scratch_bytes=0):
+    """
+    per-frame filter and smoother moments of run-length encoded profiles (bild_kalman_segments): a dict of the requested
+    outputs (names of KALMAN_OUTPUTS), each (n, T_max, d) float64; T_max defaults to the set's longest trajectory
+    """
+    seg_start, seg_state = i32(seg_start), i32(seg_state)
+    n, K1 = seg_start.shape
+    assert seg_state.shape == (n, K1)
+    tid = None if traj_id is None else i32(traj_id)
+    if T_max is None:
+        T_max = int(np.max(ts.T))
+    res = {}
+    spec = KalmanOut(T_max=int(T_max))
+    for name in outputs:
+        if name not in KALMAN_OUTPUTS:
+            raise ValueError(f"unknown output {name!r}")
+        res[name] = np.empty((n, T_max, model.d), dtype=np.float64)
+        setattr(spec, name, aptr(res[name]) if res[name].size else None)
+    check(lib().bild_kalman_segments(model._h, ts._h, n, K1, iptr(seg_start), iptr(seg_state), iptr(tid), ctypes.byref(spec),
+                                     int(scratch_bytes)))
+    return res
+
+
+def kalman_mixture(model, ts, seg_start, seg_state, log_weights, traj_id=None, scratch_bytes=0):
+    """ posterior mixture of the smoothed y per trajectory of the set (bild_kalman_mixture): (mean, var), each (n_traj, Tmax, d) """
+    seg_start, seg_state = i32(seg_start), i32(seg_state)
+    n, K1 = seg_start.shape
+    assert seg_state.shape == (n, K1)
+    lw = f64(log_weights).reshape(-1)
+    assert lw.shape == (n,)
+    tid = None if traj_id is None else i32(traj_id)
+    Tmax = int(np.max(ts.T))
+    mean = np.empty((ts.n_traj, Tmax, model.d), dtype=np.float64)
+    var = np.empty_like(mean)
+    check(lib().bild_kalman_mixture(model._h, ts._h, n, K1, iptr(seg_start), iptr(seg_state), iptr(tid), dptr(lw), dptr(mean),
+                                    dptr(var), int(scratch_bytes)))
+    return mean, var
 
 
 def prefix_info(ts):

@@ -877,6 +877,25 @@ class FixedkSampler:
         j = int(np.argmax(self._arr['logLs']))   # first occurrence of the maximum, as the reference's nested argmax
         return self.st2profile(self._pool['ss'][j], self._pool['thetas'][j])
 
+    def posterior_distance(self):
+        """
+        (mean, var), each (T, d): the smoothed distance y_t = w.x_t averaged over the pooled samples' profiles with the
+        weights `log_marginal_posterior` uses (law of total variance; MultiStateRouse.kalman_mixture).  MultiStateRouse only.
+        """
+        seg_start, seg_state, log_weights = self._posterior_segments()
+        mean, var = self.model.kalman_mixture((seg_start, seg_state), [self.traj], log_weights)
+        return mean[0], var[0]
+
+    def _posterior_segments(self):
+        """ the pooled samples as run-length segments, with their log-weights (those of log_marginal_posterior) """
+        from .models import MultiStateRouse
+        if not isinstance(self.model, MultiStateRouse):
+            raise TypeError(f"posterior distances need a MultiStateRouse model, not {type(self.model).__name__}")
+        pooled = dict(self._arr, ss=self._pool['ss'], thetas=self._pool['thetas'])
+        log_weights = pooled['log_weights'] if 'log_weights' in pooled else pooled['logLs']
+        seg_start, seg_state = segments_from_st(pooled['ss'], np.asarray(pooled['thetas']), len(self.traj))
+        return seg_start, seg_state, np.asarray(log_weights, dtype=np.float64)
+
     def log_marginal_posterior(self, native=True):
         """
         (n, T) normalised log posterior marginals of the state at each frame (bild/amis.py:945-972).

@@ -443,3 +443,59 @@ class SamplingResults:
         if dE is None:
             dE = self.dE
         return self.samplers[self.best_k(dE)].log_marginal_posterior()
+
+    def posterior_distance(self, dE=None):
+        """
+        (mean, var), each (T, d): the smoothed distance w.x averaged over the posterior of profiles, as
+        `log_marginal_posterior` averages the states -- the sampler at `best_k` by default, ``dE='average'``: all k,
+        each sampler's normalised weights times its evidence.  MultiStateRouse only.
+        """
+        seg_start, seg_state, log_weights = self._posterior_parts(dE)
+        mean, var = self.model.kalman_mixture((seg_start, seg_state), [self.traj], log_weights)
+        return mean[0], var[0]
+
+    def _posterior_parts(self, dE=None):
+        """ (seg_start, seg_state, log_weights) of the samples the posterior distance averages over """
+        if isinstance(dE, str) and dE == 'average':
+            parts = []
+            for s, logev in zip(self.samplers, self.evidence):
+                if s.evidences[-1][0] > -np.inf:
+                    a, b, lw = s._posterior_segments()
+                    parts.append((a, b, lw - logsumexp(lw) + logev))
+            return _stack_segments(parts, len(self.traj))
+        if dE is None:
+            dE = self.dE
+        return self.samplers[self.best_k(dE)]._posterior_segments()
+
+
+def _stack_segments(parts, T):
+    """ [(seg_start, seg_state, log_weights)] -> one batch, shorter profiles padded with empty segments at T """
+    K1 = max(a.shape[1] for a, _, _ in parts)
+    starts = [np.pad(a, ((0, 0), (0, K1 - a.shape[1])), constant_values=T) for a, _, _ in parts]
+    states = [np.pad(b, ((0, 0), (0, K1 - b.shape[1]))) for _, b, _ in parts]
+    return (np.concatenate(starts).astype(np.int32), np.concatenate(states).astype(np.int32),
+            np.concatenate([lw for _, _, lw in parts]))
+
+
+def posterior_distances(results, dE=None):
+    """
+    `SamplingResults.posterior_distance` of many results over one model (e.g. from `sample_many`) in ONE mixture call
+    on one trajectory set: a list of (mean, var), each (T_i, d).  ``dE`` as for `SamplingResults.posterior_distance`.
+    """
+    results = list(results)
+    if not results:
+        return []
+    model = results[0].model
+    if any(r.model is not model for r in results):
+        raise ValueError("posterior_distances needs results over one model")
+    parts, tids = [], []
+    for i, r in enumerate(results):
+        a, b, lw = r._posterior_parts(dE)
+        parts.append((a, b, lw))
+        tids.append(np.full(len(a), i, dtype=np.int32))
+    Tmax = max(len(r.traj) for r in results)
+    # (a padded segment starts at or behind its trajectory's end: it is empty either way)
+    seg_start, seg_state, log_weights = _stack_segments(parts, Tmax)
+    mean, var = model.kalman_mixture((seg_start, seg_state), [r.traj for r in results], log_weights,
+                                     traj_id=np.concatenate(tids))
+    return [(mean[i, :len(r.traj)], var[i, :len(r.traj)]) for i, r in enumerate(results)]

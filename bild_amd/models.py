@@ -299,6 +299,100 @@ class MultiStateRouse(MultiStateModel):
         """ general batch: run-length encoded profiles over a set of trajectories """
         return _lib.logl_segments(self.handle(), self.trajset(trajs), seg_start, seg_state, traj_id, path=self.path)
 
+    # ------------------------------------------------------------------ filter and smoother
+    def kalman(self, profiles, trajs, traj_id=None, outputs=('smooth',), scratch_bytes=0):
+        """
+        Per-frame moments of the Kalman filter and smoother of candidate profiles (bild_kalman_segments), for the
+        noise-free measured distance y_t = w.x_t of each dimension.
+
+        profiles : (n, T) int array or list of Loopingprofile, on the one trajectory ``trajs``; or ``(seg_start,
+            seg_state)``, each (n, K1), run-length encoded as `logL_segments` takes them, on the list ``trajs`` with
+            ``traj_id`` (n,) (None: all on the first)
+        outputs : subset of 'terms', 'pred', 'filt', 'smooth', 'innov'
+        scratch_bytes : device workspace of one chunk of the call (0: at most 1 GiB and a third of the free memory)
+
+        Returns a `KalmanResult`: the requested arrays, each (n, T_max, d), NaN behind a trajectory's own length; the
+        others are None.  The trajectory set is the one `trajset` gives (an AMIS run's set is reused); its likelihood
+        tables are neither built nor read.  Argument and envelope errors are raised before any set is created.
+        """
+        outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+        for o in outputs:
+            if o not in KalmanResult.GROUPS:
+                raise ValueError(f"unknown output {o!r}; choose from {sorted(KalmanResult.GROUPS)}")
+        items, seg_start, seg_state, tid = self._kalman_args(profiles, trajs, traj_id)
+        self._kalman_envelope()
+        names = [name for o in outputs for name in KalmanResult.GROUPS[o]]
+        ts = self.trajset(items if len(items) > 1 or isinstance(trajs, (list, tuple)) else items[0])
+        res = _lib.kalman_segments(self.handle(), ts, seg_start, seg_state, tid, outputs=names, scratch_bytes=scratch_bytes)
+        return KalmanResult(res)
+
+    def kalman_mixture(self, profiles, trajs, log_weights, traj_id=None, scratch_bytes=0):
+        """
+        Posterior mixture of the smoothed y over weighted candidates (bild_kalman_mixture): per trajectory of ``trajs``,
+        the candidates on it weighted by exp(log_weights), normalised within the trajectory.  Arguments as for `kalman`.
+        -> (mean, var), each (n_traj, T_max, d); NaN for a trajectory without candidates of finite weight.
+        """
+        items, seg_start, seg_state, tid = self._kalman_args(profiles, trajs, traj_id)
+        log_weights = np.asarray(log_weights, dtype=np.float64).reshape(-1)
+        if log_weights.shape != (len(seg_start),):
+            raise ValueError(f"{len(log_weights)} log-weights for {len(seg_start)} candidates")
+        if np.any(np.isnan(log_weights)) or np.any(log_weights == np.inf):
+            raise ValueError("log-weights must be finite or -inf (NaN or +inf given)")
+        self._kalman_envelope()
+        ts = self.trajset(items if len(items) > 1 or isinstance(trajs, (list, tuple)) else items[0])
+        return _lib.kalman_mixture(self.handle(), ts, seg_start, seg_state, log_weights, tid, scratch_bytes=scratch_bytes)
+
+    def _kalman_args(self, profiles, trajs, traj_id):
+        """ -> (trajectories, seg_start, seg_state, traj_id or None), checked on the host """
+        items = list(trajs) if isinstance(trajs, (list, tuple)) else [trajs]
+        if not items:
+            raise ValueError("need at least one trajectory")
+        lengths = [len(t) for t in items]
+        if isinstance(profiles, tuple) and len(profiles) == 2 and not isinstance(profiles[0], Loopingprofile):
+            seg_start = np.ascontiguousarray(profiles[0], dtype=np.int32)
+            seg_state = np.ascontiguousarray(profiles[1], dtype=np.int32)
+            if seg_start.ndim != 2 or seg_start.shape != seg_state.shape or seg_start.shape[1] < 1:
+                raise ValueError(f"seg_start {seg_start.shape} and seg_state {seg_state.shape} must both be (n, K1)")
+            n = len(seg_start)
+            if traj_id is not None:
+                traj_id = np.ascontiguousarray(traj_id, dtype=np.int32).reshape(-1)
+                if traj_id.shape != (n,):
+                    raise ValueError(f"traj_id has {traj_id.size} entries for {n} candidates")
+                if n and (traj_id.min() < 0 or traj_id.max() >= len(items)):
+                    raise ValueError(f"traj_id out of range for {len(items)} trajectories")
+            if n and (np.any(seg_start[:, 0] != 0) or np.any(np.diff(seg_start, axis=1) < 0) or np.any(seg_start[:, 1:] < 1)):
+                raise ValueError("segment starts must begin at 0 and be non-decreasing (later starts >= 1)")
+            if n and (seg_state.min() < 0 or seg_state.max() >= self.nStates):
+                raise ValueError(f"states out of range ({self.nStates} states)")
+            return items, seg_start, seg_state, traj_id
+        if traj_id is not None:
+            raise ValueError("traj_id goes with (seg_start, seg_state) profiles")
+        if len(items) != 1:
+            raise ValueError("expanded profiles refer to one trajectory")
+        states = profiles if isinstance(profiles, np.ndarray) else np.stack([np.asarray(p[:]) for p in profiles])
+        states = np.atleast_2d(np.asarray(states))
+        if states.ndim != 2 or states.shape[1] != lengths[0]:
+            raise ValueError(f"profiles of shape {states.shape} do not match a trajectory of {lengths[0]} frames")
+        if states.size and (states.min() < 0 or states.max() >= self.nStates):
+            raise ValueError(f"states out of range ({self.nStates} states)")
+        seg_start, seg_state = segments_from_states(states.astype(np.int32))
+        return items, seg_start, seg_state, None
+
+    def _kalman_envelope(self):
+        """ the smoother's envelope (csrc/kalman.cpp), checked on the model handle alone: no device work """
+        h = self.handle()
+        why = None
+        if not h.query(_lib.Q_MODAL_OK):
+            why = "the smoother needs the modal path, which this model lacks (B, Sig or C0 not symmetric, or no common eigenbasis)"
+        elif h.query(_lib.Q_NEFF) > 32:
+            why = f"the smoother supports at most 32 effective modes; this model has {h.query(_lib.Q_NEFF)}"
+        elif h.query(_lib.Q_D) > 8:
+            why = f"the smoother supports at most 8 dimensions; d = {h.query(_lib.Q_D)}"
+        elif h.query(_lib.Q_S) > 255:
+            why = f"the smoother supports at most 255 states; S = {h.query(_lib.Q_S)}"
+        if why is not None:
+            raise _lib.BildAmdError(_lib.ERR_UNSUPPORTED, why)
+
     # ------------------------------------------------------------------ generative model
     def initial_loopingprofile(self, traj):
         """ initial guess: the per-frame best state of the factorized model (reference bild/models.py:280-293) """
@@ -425,6 +519,25 @@ class MultiStateRouse(MultiStateModel):
                                     V.T @ m._dynamics['G'], V.T @ m._dynamics['M0'])):
                 lst.append(a)
         return [np.ascontiguousarray(np.stack(lst), dtype=np.float64) for lst in out]
+
+
+class KalmanResult:
+    """
+    Per-frame moments of `MultiStateRouse.kalman`, each (n, T_max, d) float64 or None when not requested:
+    ``terms`` (log-likelihood of each observation, 0.0 on missing frames), ``pred_mean`` / ``pred_var`` (the observation
+    given the frames before), ``filt_mean`` / ``filt_var`` and ``smooth_mean`` / ``smooth_var`` (the noise-free y = w.x
+    given the frames up to t / all frames), ``innov`` (standardised one-step-ahead innovations, NaN on missing frames).
+    """
+    GROUPS = {'terms': ('terms',), 'pred': ('pred_mean', 'pred_var'), 'filt': ('filt_mean', 'filt_var'),
+              'smooth': ('smooth_mean', 'smooth_var'), 'innov': ('innov',)}
+
+    def __init__(self, arrays):
+        for name in _lib.KALMAN_OUTPUTS:
+            setattr(self, name, arrays.get(name))
+
+    def __repr__(self):
+        have = [n for n in _lib.KALMAN_OUTPUTS if getattr(self, n) is not None]
+        return f"KalmanResult({', '.join(have)})"
 
 
 # replay mode: host memory of the normals handed to the library in one call

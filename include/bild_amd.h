@@ -669,6 +669,41 @@ int bild_rouse_simulate(int S, int N, int d, const double *V, const double *b, c
                         const uint8_t *missing, const double *loc_err, const double *normals, uint64_t seed,
                         int64_t scratch_bytes, double *out);
 
+/* ---------------------------------------------------------------- Kalman filter and smoother ---------
+ * Per-frame moments of candidate profiles on a trajectory set (MultiStateRouse.kalman): the filter of the likelihood
+ * entries (same conventions: frame 0 starts from the steady state of state[0], frame t >= 1 is predicted with the state of
+ * frame t, a frame with a NaN coordinate is predicted but not updated, one covariance per distinct localization error) and
+ * the modified Bryson-Frazier smoother behind it, which inverts no predicted covariance.  Profiles as for
+ * bild_logl_segments (n x K1, traj_id may be NULL).  Each output is n x T_max x d, frame-major per candidate; NaN behind
+ * a candidate's own T; a NULL pointer is not computed.  For frame t, dimension k, y = w.x the noise-free measurement:
+ *   terms                 -(e^2 / S + log S + log 2 pi) / 2 on observed frames, 0.0 on missing ones (summed: the logL)
+ *   pred_mean, pred_var   mean and variance of the observation x_t given the frames before t (at t = 0 the steady state)
+ *   filt_mean, filt_var   mean and variance of y_t given the frames up to t
+ *   smooth_mean, smooth_var   the same given all frames
+ *   innov                 standardized innovation (x_t - pred_mean) / sqrt(pred_var) on observed frames, NaN on missing
+ * Envelope: the modal path, <= 32 effective modes (BILD_Q_NEFF), d <= 8, S <= 255, else BILD_ERR_UNSUPPORTED before any
+ * device work.  A candidate's outputs are a pure function of (model, trajectory, profile): bit-identical whatever the
+ * batch, its order, the chunking and the other trajectories of the set.  The call runs in chunks of whole candidates
+ * whose workspace (records of the forward pass, about (L + 10) doubles per frame and chain, L = 8, 16 or 32 the modes
+ * rounded up, and the outputs) fits scratch_bytes; 0: at most 1 GiB and a third of the free device memory.  The tables
+ * of the set are neither built nor read.  Synchronous. */
+typedef struct bild_kalman_out {
+    double *terms, *pred_mean, *pred_var, *filt_mean, *filt_var, *smooth_mean, *smooth_var, *innov;
+    int32_t T_max; /* frames per candidate in the outputs: >= T of every candidate's trajectory */
+} bild_kalman_out;
+int bild_kalman_segments(const bild_model *m, const bild_trajset *ts, int64_t n, int K1, const int32_t *seg_start,
+                         const int32_t *seg_state, const int32_t *traj_id, const bild_kalman_out *out, int64_t scratch_bytes);
+/* The posterior mixture of the smoothed y over the candidates of each trajectory of the set, weights exp(log_weights)
+ * normalised within the trajectory: mean = sum w m / W, var = sum w v / W + sum w (m - mean)^2 / W (law of total
+ * variance), accumulated around the smoothed mean of the trajectory's highest-weight candidate (the first of them).
+ * mean, var: n_traj x Tmax x d, Tmax the set's longest trajectory; NaN behind a trajectory's T and for a trajectory
+ * without candidates or with all log-weights -inf.  NaN or +inf log-weights: BILD_ERR_INVALID.  The sums run in fixed
+ * blocks of 64 of a trajectory's candidates in index order, so the result does not depend on the chunking; per-candidate
+ * outputs stay on the device and only a chunk of them exists at a time. */
+int bild_kalman_mixture(const bild_model *m, const bild_trajset *ts, int64_t n, int K1, const int32_t *seg_start,
+                        const int32_t *seg_state, const int32_t *traj_id, const double *log_weights, double *mean, double *var,
+                        int64_t scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
