@@ -12,7 +12,7 @@ both evaluated by hand-written HIP kernels for gfx950 through the C ABI declared
 """
 from . import rouse, profiles, util, trajectory, models, gauss, amis, choicesampler, core, postproc  # noqa: F401
 from .core import sample, sample_many, SamplingResults, posterior_distances  # noqa: F401
-from .models import MultiStateModel, MultiStateRouse, FactorizedModel, KalmanResult  # noqa: F401
+from .models import MultiStateModel, MultiStateRouse, FactorizedModel, KalmanResult, FitResult  # noqa: F401
 from .gauss import GenericGaussianModel  # noqa: F401
 from .amis import FixedkSampler, Dirichlet, CFC  # noqa: F401
 from .profiles import Loopingprofile  # noqa: F401

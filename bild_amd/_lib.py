@@ -146,6 +146,9 @@ _SIGNATURES = {
     # Kalman filter and smoother (kalman.cpp)
     'bild_kalman_segments': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, _vp, ctypes.c_int64]),
     'bild_kalman_mixture': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, _dp, _dp, _dp, ctypes.c_int64]),
+    # log-likelihood sensitivities (sens.cpp)
+    'bild_logl_sensitivities': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, ctypes.c_int, _vp, _dp,
+                                               _dp, _dp, _dp, ctypes.c_int64]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -587,6 +590,51 @@ def kalman_mixture(model, ts, seg_start, seg_state, log_weights, traj_id=None, s
     check(lib().bild_kalman_mixture(model._h, ts._h, n, K1, iptr(seg_start), iptr(seg_state), iptr(tid), dptr(lw), dptr(mean),
                                     dptr(var), int(scratch_bytes)))
     return mean, var
+
+
+class ModelDerivs(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('dB', 'dG', 'dSig', 'dM0', 'dC0')]
+
+
+DERIV_NAMES = ('dB', 'dG', 'dSig', 'dM0', 'dC0')
+
+
+def logl_sensitivities(model, ts, seg_start, seg_state, traj_id=None, derivs=None, ds2=None, P=None, grad=True, fisher=True,
+                       scratch_bytes=0):
+    """
+    log-likelihood, gradient and Fisher information of run-length encoded profiles (bild_logl_sensitivities).
+    derivs: dict of raw derivative arrays (DERIV_NAMES; each (P, S, N, N) or (P, S, N, d), absent = zero); ds2:
+    (P, n_traj, d) or None.  -> (logl (n,), grad (n, P) or None, fisher (n, P, P) or None)
+    """
+    seg_start, seg_state = i32(seg_start), i32(seg_state)
+    n, K1 = seg_start.shape
+    assert seg_state.shape == (n, K1)
+    tid = None if traj_id is None else i32(traj_id)
+    derivs = {} if derivs is None else derivs
+    unknown = set(derivs) - set(DERIV_NAMES)
+    if unknown:
+        raise ValueError(f"unknown derivative arrays {sorted(unknown)}; choose from {DERIV_NAMES}")
+    arrs = {k: f64(v) for k, v in derivs.items() if v is not None}
+    if P is None:
+        P = next((len(a) for a in arrs.values()), len(ds2) if ds2 is not None else 0)
+    S, N, d = model.S, model.N, model.d
+    for k, a in arrs.items():
+        want = (P, S, N, N) if k in ('dB', 'dSig', 'dC0') else (P, S, N, d)
+        if a.shape != want:
+            raise ValueError(f"{k} has shape {a.shape}, expected {want}")
+    spec = ModelDerivs(**{k: aptr(a) if a.size else None for k, a in arrs.items()})
+    if ds2 is not None:
+        ds2 = f64(ds2)
+        if ds2.shape != (P, ts.n_traj, d):
+            raise ValueError(f"ds2 has shape {ds2.shape}, expected {(P, ts.n_traj, d)}")
+    logl = np.empty(n, dtype=np.float64)
+    g = np.empty((n, P), dtype=np.float64) if grad else None
+    F = np.empty((n, P, P), dtype=np.float64) if fisher else None
+    check(lib().bild_logl_sensitivities(model._h, ts._h, n, K1, iptr(seg_start), iptr(seg_state), iptr(tid), int(P),
+                                        ctypes.byref(spec), None if ds2 is None or not ds2.size else dptr(ds2), dptr(logl),
+                                        None if g is None or not g.size else dptr(g),
+                                        None if F is None or not F.size else dptr(F), int(scratch_bytes)))
+    return logl, g, F
 
 
 def prefix_info(ts):

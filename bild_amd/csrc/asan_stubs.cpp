@@ -6,6 +6,7 @@
 #include "amis_math.h"
 #include "internal.h"
 #include "kalman.h"
+#include "sens.h"
 
 namespace bild {
 int padded_rows(int n)
@@ -36,6 +37,7 @@ int launch_logl_wide(int, const KParams &, int, void *) { return 1; }
 int launch_walk(const WalkParams &, void *, void *, void *) { return 1; }
 int launch_kalman(const KalParams &, int, void *) { return 1; }
 int launch_kalman_mix(const MixParams &, void *) { return 1; }
+int launch_sens(const SensParams &, int, int, void *) { return 1; }
 int launch_tail(const TrajDesc *, int, int, int, int, int, const double *, const double *, const int64_t *, int64_t, double *, double *, void *) { return 1; }
 int launch_mark_refused_rows(const int32_t *, int, int64_t, double *, void *) { return 1; }
 int amis_dev_pass_a_rows(int64_t, int64_t) { return 0; }

@@ -4,12 +4,10 @@
 #include "kalman.h"
 #include "sim_host.h"
 
-namespace {
-
-using namespace bild;
+namespace bild {
 
 // the envelope of the kernel, checked before any device work
-int check_model(const bild_model *m)
+static int check_model(const bild_model *m)
 {
     if (!m->modal_ok) return fail(BILD_ERR_UNSUPPORTED, "the smoother needs the modal path, which this model lacks: %s", m->modal_why.c_str());
     if (m->n > kKalMaxModes)
@@ -19,8 +17,8 @@ int check_model(const bild_model *m)
     return BILD_OK;
 }
 
-int check_args(const bild_model *m, const bild_trajset *ts, int64_t n, int K1, const int32_t *seg_start, const int32_t *seg_state,
-               const int32_t *traj_id, int64_t scratch_bytes)
+int kalman_check_args(const bild_model *m, const bild_trajset *ts, int64_t n, int K1, const int32_t *seg_start, const int32_t *seg_state,
+                      const int32_t *traj_id, int64_t scratch_bytes)
 {
     if (!m || !ts) return fail(BILD_ERR_INVALID, "NULL handle");
     if (ts->model != m) return fail(BILD_ERR_INVALID, "trajectory set belongs to a different model");
@@ -46,6 +44,12 @@ int check_args(const bild_model *m, const bild_trajset *ts, int64_t n, int K1, c
     if (dev != ts->device) return fail(BILD_ERR_INVALID, "trajectory set lives on device %d, current device is %d", ts->device, dev);
     return BILD_OK;
 }
+
+} // namespace bild
+
+namespace {
+
+using namespace bild;
 
 // One call's device state: the model's modal arrays padded to L lanes, the workspace of the records, the segment lists
 struct KalCall {
@@ -153,7 +157,7 @@ extern "C" int bild_kalman_segments(const bild_model *m, const bild_trajset *ts,
                                     const int32_t *seg_state, const int32_t *traj_id, const bild_kalman_out *out,
                                     int64_t scratch_bytes)
 {
-    int rc = check_args(m, ts, n, K1, seg_start, seg_state, traj_id, scratch_bytes);
+    int rc = kalman_check_args(m, ts, n, K1, seg_start, seg_state, traj_id, scratch_bytes);
     if (rc) return rc;
     if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
     double *const host_out[kKalOutputs] = {out->terms, out->pred_mean, out->pred_var, out->filt_mean,
@@ -209,7 +213,7 @@ extern "C" int bild_kalman_mixture(const bild_model *m, const bild_trajset *ts, 
                                    const int32_t *seg_state, const int32_t *traj_id, const double *log_weights, double *mean,
                                    double *var, int64_t scratch_bytes)
 {
-    int rc = check_args(m, ts, n, K1, seg_start, seg_state, traj_id, scratch_bytes);
+    int rc = kalman_check_args(m, ts, n, K1, seg_start, seg_state, traj_id, scratch_bytes);
     if (rc) return rc;
     if (!mean || !var || (n > 0 && !log_weights)) return fail(BILD_ERR_INVALID, "NULL buffer");
     for (int64_t r = 0; r < n; ++r)

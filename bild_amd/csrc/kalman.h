@@ -5,6 +5,9 @@
 
 #include "common.h"
 
+struct bild_model;
+struct bild_trajset;
+
 namespace bild {
 
 constexpr int kKalMaxModes = 32;  // effective modes (BILD_Q_NEFF) of the modal chain one task carries, one lane per mode
@@ -32,6 +35,10 @@ struct KalParams {
     double *out[kKalOutputs]; // (n, Tout, d) each, null: not wanted
 };
 int launch_kalman(const KalParams &p, int L, void *stream);
+// the arguments and the envelope of a call (kalman.cpp), checked before any device work; also what
+// bild_logl_sensitivities accepts (sens.cpp)
+int kalman_check_args(const bild_model *m, const bild_trajset *ts, int64_t n, int K1, const int32_t *seg_start,
+                      const int32_t *seg_state, const int32_t *traj_id, int64_t scratch_bytes);
 
 struct MixParams {
     const double *mean, *var; // the chunk's smoothed outputs, (n, Tout, d)

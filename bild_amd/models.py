@@ -76,6 +76,8 @@ class MultiStateRouse(MultiStateModel):
                  path='auto',
                  ):
         self._d = d
+        # what with_parameters needs to rebuild the model (looppositions are not stored otherwise)
+        self._ctor = dict(N=N, D=D, k=k, d=d, looppositions=tuple(looppositions), measurement=measurement, path=path)
 
         if str(measurement) == "end2end":
             measurement = np.zeros(N)
@@ -393,6 +395,201 @@ class MultiStateRouse(MultiStateModel):
         if why is not None:
             raise _lib.BildAmdError(_lib.ERR_UNSUPPORTED, why)
 
+    # ------------------------------------------------------------------ parameter sensitivities and fit
+    PARAMS = ('D', 'k', 'localization_error')
+
+    def logL_sensitivities(self, profiles, trajs, params=('D', 'k', 'localization_error'), traj_id=None, log=True, fisher=True,
+                           scratch_bytes=0, derivatives=None):
+        """
+        Log-likelihood of candidate profiles with its gradient and Fisher information with respect to model parameters
+        (bild_logl_sensitivities: forward sensitivities of the filter).
+
+        profiles, trajs, traj_id : as for `kalman`
+        params : names out of 'D', 'k', 'localization_error' (at most 4).  'localization_error' is one sigma shared by all
+            dimensions: the model's own when it has one, else each trajectory's (which must then be equal across its
+            dimensions).  Models built with `from_arrays` / `from_reference` have no D or k: pass ``derivatives`` instead.
+        log : differentiate with respect to log theta (the gradient times theta, the Fisher entries times theta_p theta_q)
+        fisher : compute the Fisher information (innovations form: sum over observed frames and dimensions of
+            dS_p dS_q / (2 S^2) + de_p de_q / S)
+        derivatives : raw derivatives instead of ``params`` -- a dict with any of dB, dSig, dC0 (P, S, N, N), dG, dM0
+            (P, S, N, d) and ds2 (P, n_traj, d: the derivative of the variance of each dimension of each trajectory); then
+            ``log`` must be False
+
+        Returns (logL (n,), grad (n, P), fisher (n, P, P) or None).
+        """
+        items, seg_start, seg_state, tid = self._kalman_args(profiles, trajs, traj_id)
+        if derivatives is not None:
+            if log:
+                raise ValueError("raw derivatives are derivatives with respect to theta: pass log=False with them")
+            derivs = {k: v for k, v in derivatives.items() if k != 'ds2'}
+            ds2 = derivatives.get('ds2')
+            lens = {len(np.asarray(v)) for v in derivatives.values() if v is not None}
+            if len(lens) > 1:
+                raise ValueError(f"derivative arrays disagree on the number of parameters: {sorted(lens)}")
+            P = lens.pop() if lens else 0
+            theta = None
+        else:
+            params = self._check_params(params)
+            P = len(params)
+            derivs, ds2, theta = self._derivatives(params, items)
+        if P > 4:
+            raise _lib.BildAmdError(_lib.ERR_UNSUPPORTED, f"at most 4 parameters per call; {P} given")
+        self._kalman_envelope()
+        if P > 0 and self.handle().query(_lib.Q_NEFF) > 16:
+            raise _lib.BildAmdError(_lib.ERR_UNSUPPORTED, f"models of 17 to 32 effective modes (this one has "
+                                    f"{self.handle().query(_lib.Q_NEFF)}) support no parameters; {P} given")
+        ts = self.trajset(items if len(items) > 1 or isinstance(trajs, (list, tuple)) else items[0])
+        logl, grad, F = _lib.logl_sensitivities(self.handle(), ts, seg_start, seg_state, tid, derivs=derivs, ds2=ds2, P=P,
+                                                fisher=fisher, scratch_bytes=scratch_bytes)
+        if log and P:
+            th = theta[np.zeros(len(logl), dtype=int) if tid is None else tid]     # (n, P): theta of each candidate
+            grad, F = _log_chain_rule(grad, F, th)
+        return logl, grad, F
+
+    def _check_params(self, params):
+        params = (params,) if isinstance(params, str) else tuple(params)
+        for p in params:
+            if p not in self.PARAMS:
+                raise ValueError(f"unknown parameter {p!r}; choose from {self.PARAMS}")
+        if len(set(params)) != len(params):
+            raise ValueError(f"parameters repeat: {params}")
+        if self.models is None and any(p in ('D', 'k') for p in params):
+            raise ValueError("this model was built from arrays (from_arrays / from_reference): it has no D or k; "
+                             "pass derivatives= with the raw derivative arrays instead")
+        return params
+
+    def _sigma(self, items):
+        """ the one localization error per trajectory that 'localization_error' differentiates (n_traj,) """
+        sig = []
+        for t in items:
+            err = np.asarray(self._get_noise(t), dtype=np.float64).reshape(-1)
+            if err.size != 1 and np.any(err != err[0]):
+                raise ValueError(f"'localization_error' is one sigma shared by all dimensions; this trajectory has {err}")
+            sig.append(float(err[0]))
+        return np.array(sig)
+
+    def _derivatives(self, params, items):
+        """ -> (raw derivative arrays, ds2 (P, n_traj, d) or None, theta (n_traj, P)) """
+        S, N, d = self.nStates, len(self.measurement), self.d
+        derivs = {k: np.zeros((len(params), S, N, N if k in ('dB', 'dSig', 'dC0') else d)) for k in _lib.DERIV_NAMES}
+        ds2 = None
+        theta = np.zeros((len(items), len(params)))
+        for p, name in enumerate(params):
+            if name == 'localization_error':
+                sig = self._sigma(items)
+                ds2 = np.zeros((len(params), len(items), d)) if ds2 is None else ds2
+                ds2[p] = 2. * sig[:, None]
+                theta[:, p] = sig
+                continue
+            for s, m in enumerate(self.models):
+                for k, v in m.dynamics_derivatives(name).items():
+                    derivs[k][p, s] = v
+            theta[:, p] = self._ctor[name]
+        return derivs, ds2, theta
+
+    def with_parameters(self, D=None, k=None, localization_error=None):
+        """ a new model with the same bonds, measurement, d and path, and the parameters given replaced """
+        if self.models is None:
+            raise ValueError("this model was built from arrays (from_arrays / from_reference): it has no D or k to replace")
+        c = dict(self._ctor)
+        if D is not None:
+            c['D'] = float(D)
+        if k is not None:
+            c['k'] = float(k)
+        err = self.localization_error if localization_error is None else localization_error
+        out = MultiStateRouse(c['N'], c['D'], c['k'], d=c['d'], looppositions=c['looppositions'], measurement=self.measurement,
+                              localization_error=err, path=c['path'])
+        out.transitions = self.transitions.copy()
+        return out
+
+    def fit(self, trajs, profiles, params=('D', 'k', 'localization_error'), start=None, tol=1e-8, max_iter=50):
+        """
+        Maximum-likelihood fit of the parameters ``params`` (out of 'D', 'k', 'localization_error') on trajectories whose
+        looping profiles are known, by Fisher scoring in log theta with Levenberg damping.
+
+        trajs : list of trajectories
+        profiles : one per trajectory (a `Loopingprofile`, a 1-d integer array, or ``(seg_start, seg_state)`` of shape
+            (n_traj, K1) for all of them), or a single state index: a constant profile
+        start : dict of starting values (default: this model's)
+        tol, max_iter : the fit stops when the Newton decrement g^T F^-1 g / 2 falls below ``tol``, or after ``max_iter``
+            device calls
+
+        Every iteration is one `logL_sensitivities` call over all trajectories; a step is accepted only if the total
+        logL rises, else the damping grows.  A call builds the model at the trial parameters on the host and uploads the
+        trajectories again (a new model has a new trajectory set): for N = 20 that is well under a millisecond of model
+        analysis per call, and the upload is one copy of the data.  Parameters not listed stay as they are.  Fitting
+        'localization_error' sets the model-level localization error, which takes precedence over the trajectories' own
+        (reference bild/models.py:255-263); without it the noise in force stays what it was.
+
+        Returns a `FitResult`: the fitted model, params, standard errors (inverse Fisher information at the optimum, by
+        the delta method from log theta), their covariance, logL, n_iter, converged and the history.
+        """
+        params = self._check_params(params)
+        if not params:
+            raise ValueError("nothing to fit: params is empty")
+        if len(params) > 4:
+            raise ValueError("at most 4 parameters")
+        if self.models is None:
+            raise ValueError("this model was built from arrays (from_arrays / from_reference): it cannot be refitted")
+        items = list(trajs) if isinstance(trajs, (list, tuple)) else [trajs]
+        if not items:
+            raise ValueError("need at least one trajectory")
+        seg = _fit_profiles(profiles, [len(t) for t in items], self.nStates)
+        if tol <= 0 or max_iter < 1:
+            raise ValueError("need tol > 0 and max_iter >= 1")
+        cur = self._current_params(items, params)
+        start = {} if start is None else dict(start)
+        for kname in start:
+            if kname not in params:
+                raise ValueError(f"start value for {kname!r}, which is not fitted")
+        theta = np.array([float(start.get(p, cur[p])) for p in params])
+        if np.any(~np.isfinite(theta)) or np.any(theta <= 0):
+            raise ValueError(f"parameters must be positive and finite: {dict(zip(params, theta))}")
+        tid = np.arange(len(items), dtype=np.int32)
+
+        def evaluate(th):
+            model = self._model_at(params, th)
+            logl, g, F = model.logL_sensitivities(seg, items, params=params, traj_id=tid, log=True)
+            return model, float(logl.sum()), g.sum(axis=0), F.sum(axis=0)
+
+        model, L, g, F = evaluate(theta)
+        history = [(dict(zip(params, theta)), L)]
+        mu, n_iter, converged = 0.0, 1, False
+        while True:
+            dec = _newton_decrement(g, F)
+            if dec < tol:
+                converged = True
+                break
+            if n_iter >= max_iter:
+                break
+            step = _damped_step(g, F, mu)
+            trial = theta * np.exp(step)
+            tm, tL, tg, tF = evaluate(trial)
+            n_iter += 1
+            if np.isfinite(tL) and tL > L:
+                theta, model, L, g, F = trial, tm, tL, tg, tF
+                history.append((dict(zip(params, theta)), L))
+                mu = 0.0 if mu <= 1e-3 else mu / 10.
+            else:
+                mu = 1e-3 if mu == 0.0 else mu * 10.
+                if mu > 1e12:
+                    break
+        cov_log = np.linalg.pinv(F)
+        cov = cov_log * np.outer(theta, theta)
+        se = np.sqrt(np.maximum(np.diag(cov), 0.))
+        return FitResult(model=model, params=dict(zip(params, theta)), se=dict(zip(params, se)), cov=cov, logL=L,
+                         n_iter=n_iter, converged=converged, history=history, names=params)
+
+    def _current_params(self, items, params):
+        out = {'D': self._ctor['D'], 'k': self._ctor['k']}
+        if 'localization_error' in params:
+            out['localization_error'] = float(self._sigma(items)[0])
+        return out
+
+    def _model_at(self, params, theta):
+        kw = {p: float(v) for p, v in zip(params, theta)}
+        return self.with_parameters(**kw)
+
     # ------------------------------------------------------------------ generative model
     def initial_loopingprofile(self, traj):
         """ initial guess: the per-frame best state of the factorized model (reference bild/models.py:280-293) """
@@ -538,6 +735,67 @@ class KalmanResult:
     def __repr__(self):
         have = [n for n in _lib.KALMAN_OUTPUTS if getattr(self, n) is not None]
         return f"KalmanResult({', '.join(have)})"
+
+
+class FitResult:
+    """
+    `MultiStateRouse.fit`: ``model`` (at the fitted parameters), ``params`` and ``se`` (dicts by name), ``cov`` (P x P, in
+    the order of ``names``), ``logL`` (total at the optimum), ``n_iter`` (device calls), ``converged``, ``history``
+    (accepted (params, logL) in order, the start first)
+    """
+
+    def __init__(self, model, params, se, cov, logL, n_iter, converged, history, names):
+        self.model, self.params, self.se, self.cov, self.logL = model, params, se, cov, logL
+        self.n_iter, self.converged, self.history, self.names = n_iter, converged, history, tuple(names)
+
+    def __repr__(self):
+        ps = ', '.join(f"{k}={v:.6g}+-{self.se[k]:.2g}" for k, v in self.params.items())
+        return f"FitResult({ps}, logL={self.logL:.6f}, n_iter={self.n_iter}, converged={self.converged})"
+
+
+def _log_chain_rule(grad, fisher, theta):
+    """ derivatives with respect to theta -> with respect to log theta: grad * theta, fisher * theta_p theta_q (per row) """
+    grad = grad * theta
+    if fisher is not None:
+        fisher = fisher * theta[:, :, None] * theta[:, None, :]
+    return grad, fisher
+
+
+def _newton_decrement(g, F):
+    """ g^T F^-1 g / 2 (pseudo-inverse: a singular F is no error here) """
+    return 0.5 * float(g @ np.linalg.pinv(F) @ g)
+
+
+def _damped_step(g, F, mu):
+    """ the Levenberg-damped Fisher-scoring step (F + mu diag(F)) delta = g """
+    A = F + mu * np.diag(np.diag(F))
+    return np.linalg.lstsq(A, g, rcond=None)[0]
+
+
+def _fit_profiles(profiles, lengths, n_states):
+    """ `fit`'s profiles -> (seg_start, seg_state), one row per trajectory """
+    n = len(lengths)
+    if isinstance(profiles, (int, np.integer)):
+        if not 0 <= profiles < n_states:
+            raise ValueError(f"state {profiles} out of range ({n_states} states)")
+        return (np.zeros((n, 1), dtype=np.int32), np.full((n, 1), int(profiles), dtype=np.int32))
+    if isinstance(profiles, tuple) and len(profiles) == 2 and not isinstance(profiles[0], Loopingprofile) \
+            and np.ndim(profiles[0]) == 2:
+        seg_start = np.ascontiguousarray(profiles[0], dtype=np.int32)
+        seg_state = np.ascontiguousarray(profiles[1], dtype=np.int32)
+        if seg_start.shape != seg_state.shape or len(seg_start) != n:
+            raise ValueError(f"(seg_start, seg_state) of shapes {seg_start.shape}, {seg_state.shape} for {n} trajectories")
+        return seg_start, seg_state
+    items = list(profiles)
+    if len(items) != n:
+        raise ValueError(f"{len(items)} profiles for {n} trajectories")
+    states = [np.asarray(p[:]) for p in items]
+    for i, (st, T) in enumerate(zip(states, lengths)):
+        if st.ndim != 1 or len(st) != T or not np.issubdtype(st.dtype, np.integer):
+            raise ValueError(f"profile {i} is not an integer array of the trajectory's {T} frames")
+        if st.min() < 0 or st.max() >= n_states:
+            raise ValueError(f"profile {i} has a state outside 0 .. {n_states - 1}")
+    return _ragged_segments(states, np.array(lengths, dtype=np.int64))
 
 
 # replay mode: host memory of the normals handed to the library in one call

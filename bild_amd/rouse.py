@@ -120,6 +120,49 @@ class Model:
             'LC0': V * np.sqrt(np.maximum(cinf, 0.)),
         }
 
+    def dynamics_derivatives(self, param):
+        """
+        Derivatives of the dynamics with respect to ``param`` ('D' or 'k'): a dict with dB, dG, dSig (N, N) and dM0 (N, d),
+        dC0 (N, N), in the layout of ``_dynamics`` and ``steady_state()``.  With a = k alpha per mode (alpha an eigenvalue
+        of A) the eigenvectors do not depend on D or k, so every derivative is diagonal in the same basis:
+
+            b = exp(-a)             db/dk = -alpha b                                        db/dD = 0
+            sig = -D expm1(-2a)/a   dsig/dk = (D/k) (2 exp(-2a) + expm1(-2a)/a)              dsig/dD = sig/D
+            cinf = D/a              dcinf/dk = -cinf/k                                       dcinf/dD = 1/a
+            g = -expm1(-a)/a        dg/dk = (a/k) (exp(-a) (1 + a) - 1)/a^2                   dg/dD = 0
+            minf = 1/a              dminf/dk = -minf/k                                       dminf/dD = 0
+
+        and the pinned zero mode (sig = 2D, cinf = 0, b = g = 1, minf = 0) has dsig/dD = 2 and nothing else.  The brackets
+        that cancel for small a are summed as series there.
+        """
+        if param not in ('D', 'k'):
+            raise ValueError(f"unknown parameter {param!r}; choose 'D' or 'k'")
+        a, V = np.linalg.eigh(self.k * self.A)
+        scale = max(np.max(np.abs(a)), 1e-300)
+        zero = np.abs(a) <= _ZERO_MODE_RTOL * scale * self.N
+        a = np.where(zero, 1., a)
+        if param == 'D':
+            db = np.zeros_like(a)
+            dsig = np.where(zero, 2., -np.expm1(-2. * a) / a)
+            dcinf = np.where(zero, 0., 1. / a)
+            dg = np.zeros_like(a)
+            dminf = np.zeros_like(a)
+        else:
+            k, D = self.k, self.D
+            db = np.where(zero, 0., -(a / k) * np.exp(-a))
+            # 2 exp(-u) + 2 expm1(-u)/u at u = 2a; and h(a) = exp(-a) (1 + a) - 1
+            dsig = np.where(zero, 0., (D / k) * _two_exp_plus(2. * a))
+            dcinf = np.where(zero, 0., -(D / a) / k)
+            dg = np.where(zero, 0., _h_over_a(a) / k)
+            dminf = np.where(zero, 0., -(1. / a) / k)
+
+        def sym(diag):
+            X = (V * diag) @ V.T
+            return np.ascontiguousarray(0.5 * (X + X.T))
+
+        return {'dB': sym(db), 'dG': np.ascontiguousarray(sym(dg) @ self.F), 'dSig': sym(dsig),
+                'dM0': np.ascontiguousarray(sym(dminf) @ self.F), 'dC0': sym(dcinf)}
+
     def check_dynamics(self, run_if_necessary=True):
         if self._dynamics['needs_updating']:
             if not run_if_necessary:
@@ -164,6 +207,38 @@ class Model:
         rng = np.random.default_rng() if rng is None else rng
         return (self._dynamics['B'] @ conf + self._dynamics['G']
                 + self._dynamics['LSig'] @ rng.standard_normal((self.N, self.d)))
+
+
+def _two_exp_plus(u):
+    """ 2 exp(-u) + 2 expm1(-u)/u = (2/u) (exp(-u) (1 + u) - 1), without the cancellation at small u """
+    u = np.asarray(u, dtype=np.float64)
+    out = np.empty_like(u)
+    small = u < 0.5
+    us = np.where(small, u, 1.)
+    out[~small] = 2. * np.exp(-u[~small]) + 2. * np.expm1(-u[~small]) / u[~small]
+    out[small] = 2. * _h_series(us[small]) / us[small]
+    return out
+
+
+def _h_over_a(a):
+    """ a (exp(-a) (1 + a) - 1) / a^2 = (exp(-a) (1 + a) - 1) / a, without the cancellation at small a """
+    a = np.asarray(a, dtype=np.float64)
+    out = np.empty_like(a)
+    small = a < 0.5
+    out[~small] = (np.exp(-a[~small]) * (1. + a[~small]) - 1.) / a[~small]
+    out[small] = _h_series(a[small]) / a[small]
+    return out
+
+
+def _h_series(u):
+    """ exp(-u) (1 + u) - 1 = sum_{m >= 2} (-1)^m (1 - m) u^m / m!  for u < 0.5 (terms to m = 24: below 1e-17 relative) """
+    total = np.zeros_like(u)
+    term = np.ones_like(u)     # u^m / m!
+    for m in range(1, 25):
+        term = term * u / m
+        if m >= 2:
+            total = total + (-1) ** m * (1 - m) * term
+    return total
 
 
 def stack_dynamics(models):

@@ -704,6 +704,35 @@ int bild_kalman_mixture(const bild_model *m, const bild_trajset *ts, int64_t n, 
                         const int32_t *seg_state, const int32_t *traj_id, const double *log_weights, double *mean, double *var,
                         int64_t scratch_bytes);
 
+/* ---------------------------------------------------------------- log-likelihood sensitivities ------
+ * The log-likelihood of candidate profiles (the filter of bild_logl_segments, run as bild_kalman_segments runs it) with
+ * its gradient and the innovations form of its Fisher information with respect to P <= 4 parameters theta_p, by forward
+ * sensitivities of the filter in the modal basis of each state.  The caller gives the derivatives of the model arrays:
+ * each member of bild_model_derivs is P x (the shape of the array of bild_model_create: S x N x N for dB, dSig, dC0,
+ * S x N x d for dG, dM0), row-major, NULL = zero; ds2 is P x n_traj x d, the derivative of the variance of dimension k of
+ * trajectory j (the square of its localization error), NULL = zero.  Per candidate r (traj_id may be NULL):
+ *   logl[r]                  sum over frames and dimensions of the terms of bild_kalman_segments (equal to bild_logl_segments
+ *                            to rounding, not bit for bit)
+ *   grad[r * P + p]          d logl / d theta_p
+ *   fisher[(r * P + p) * P + q]   sum over observed frames and dimensions of dS_p dS_q / (2 S^2) + de_p de_q / S, S the
+ *                            innovation variance and e the innovation: positive semi-definite, and its expectation over
+ *                            the data is the Fisher information
+ * NULL outputs are not computed.  The derivatives are projected into the model's reduced coordinates and each state's modal
+ * basis once per call; BILD_ERR_UNSUPPORTED, with the residual in the message and before any device work, when one leaves
+ * the reduced subspace, when a dB or dSig is not diagonal in a state's modal basis (relative residual above 1e-9: the
+ * parameter moves the eigenvectors -- bond strengths, loop positions, N, the measurement), or when two dimensions of one
+ * covariance chain (equal localization errors) have different ds2.  Envelope: that of bild_kalman_segments, 0 <= P <= 4,
+ * and P = 0 for models of 17 to 32 effective modes.  A candidate's results are a pure function of (model, trajectory,
+ * profile, derivatives): bit-identical whatever the batch, its order, the chunking and the other trajectories of the set.
+ * The call runs in chunks of whole candidates within scratch_bytes (0: at most 1 GiB and a third of the free device
+ * memory); the tables of the set are neither built nor read.  Synchronous. */
+typedef struct bild_model_derivs {
+    const double *dB, *dG, *dSig, *dM0, *dC0;
+} bild_model_derivs;
+int bild_logl_sensitivities(const bild_model *m, const bild_trajset *ts, int64_t n, int K1, const int32_t *seg_start,
+                            const int32_t *seg_state, const int32_t *traj_id, int P, const bild_model_derivs *dm,
+                            const double *ds2, double *logl, double *grad, double *fisher, int64_t scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
