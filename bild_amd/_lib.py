@@ -149,6 +149,9 @@ _SIGNATURES = {
     # log-likelihood sensitivities (sens.cpp)
     'bild_logl_sensitivities': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, ctypes.c_int, _vp, _dp,
                                                _dp, _dp, _dp, ctypes.c_int64]),
+    # GenericGaussianModel log-likelihood sensitivities (gauss_sens.cpp)
+    'bild_gauss_logl_sensitivities': (ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip,
+                                                     ctypes.c_int, _vp, _dp, _dp, _dp, ctypes.c_int64]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -634,6 +637,43 @@ def logl_sensitivities(model, ts, seg_start, seg_state, traj_id=None, derivs=Non
                                         ctypes.byref(spec), None if ds2 is None or not ds2.size else dptr(ds2), dptr(logl),
                                         None if g is None or not g.size else dptr(g),
                                         None if F is None or not F.size else dptr(F), int(scratch_bytes)))
+    return logl, g, F
+
+
+class GaussDerivs(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('dmsd', 'dmsd_inf', 'dmean')]
+
+
+def gauss_logl_sensitivities(model, trajs, seg_start, seg_state, traj_id=None, dmsd=None, dmsd_inf=None, dmean=None, P=0,
+                             fisher=True, scratch_bytes=0):
+    """
+    log-likelihood, gradient and Fisher information of GenericGaussianModel candidates (bild_gauss_logl_sensitivities) of
+    the model handle ``model``: trajs a list of (T, d) arrays, segments (n, K1); dmsd (P, S, d, Tmax + 1), dmsd_inf and
+    dmean (P, S, d), None = zero.  -> (logl (n,), grad (n, P), fisher (n, P, P) or None)
+    """
+    seg_start, seg_state = i32(seg_start), i32(seg_state)
+    n, K1 = seg_start.shape
+    assert seg_state.shape == (n, K1)
+    tid = None if traj_id is None else i32(traj_id)
+    assert tid is None or tid.shape == (n,)
+    arrs = [f64(t) for t in trajs]
+    T = i32([a.shape[0] for a in arrs])
+    x = f64(np.concatenate(arrs, axis=0))
+    S, d, L1 = model.S, model.d, model.Tmax + 1
+    keep = {}
+    for name, a, shape in (('dmsd', dmsd, (P, S, d, L1)), ('dmsd_inf', dmsd_inf, (P, S, d)), ('dmean', dmean, (P, S, d))):
+        if a is not None:
+            a = f64(a)
+            assert a.shape == shape, f"{name} has shape {a.shape}, expected {shape}"
+            keep[name] = a
+    spec = GaussDerivs(**{k: aptr(a) if a.size else None for k, a in keep.items()})
+    logl = np.empty(n, dtype=np.float64)
+    g = np.empty((n, P), dtype=np.float64)
+    F = np.empty((n, P, P), dtype=np.float64) if fisher else None
+    check(lib().bild_gauss_logl_sensitivities(model._h, len(arrs), iptr(T), dptr(x), n, K1, iptr(seg_start), iptr(seg_state),
+                                              iptr(tid), int(P), ctypes.byref(spec), dptr(logl),
+                                              dptr(g) if g.size else None, dptr(F) if F is not None and F.size else None,
+                                              int(scratch_bytes)))
     return logl, g, F
 
 

@@ -56,6 +56,8 @@ int launch_gauss_factor_sets(const GaussJobSet *, const GaussJob *, int, void *)
 int launch_gauss_sim_normals(const GaussSimProduct &, void *) { return 1; }
 int launch_gauss_sim_product(const GaussSimProduct &, void *) { return 1; }
 int launch_gauss_sim_assemble(const GaussSimAssemble &, void *) { return 1; }
+int launch_gauss_sens_factor(const GaussSensSet *, const GaussSensJob *, int, int, double *, double *, void *) { return 1; }
+int launch_gauss_sens_solve(const GaussSensSet *, const GaussSensJob *, int, int, int, double *, void *) { return 1; }
 } // namespace bild
 #include "exchange.h"
 namespace bild {

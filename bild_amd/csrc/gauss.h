@@ -128,6 +128,38 @@ struct GaussSimAssemble {
     int n, d;
 };
 
+// The sensitivities (gauss_sens.cpp; kernels in gauss_sens.hip).  One set per (trajectory,
+// dimension, state) that a window uses, and one per (state, dimension, parameter) of a shared factor.
+constexpr int kGaussSensMaxP = 4;
+constexpr int kGaussSensStride = 16;    // doubles per job output: sum tau, sum dtau_p (4), Fisher upper triangle (10), pad
+
+struct GaussSensSet {
+    const int32_t *vidx;        // valid frames of the dimension, ascending
+    const double *xv;           // their values
+    const double *msd;          // the state's MSD at lags 0 .. Tmax
+    const double *dmsd;         // its derivatives: P rows of dmsd_ld doubles
+    int64_t dmsd_ld;
+    double msd_inf, mean;
+    double dmsd_inf[kGaussSensMaxP], dmean[kGaussSensMaxP];
+    const double *fac;          // the shared factor of (state, dimension) (gap-free jobs; layout: gauss_sens_solve_kernel)
+    int fac_ld, order;
+};
+
+struct GaussSensJob {
+    int set;
+    int rank;           // rank of the window's first valid frame among the dimension's valid frames
+    int n;              // entries the job runs: up to the window's last counted entry
+    int skip;           // first counted entry (1: a later ss_order-0 interval, whose entry 0 is the conditioning value)
+    int centred;        // ss_order 0: the first value is centred as well (the first interval)
+    int out;            // output row (kGaussSensStride doubles); -1: a shared factor (no data row, no output)
+    int64_t fac;        // the job's factor at base + fac: (rows x n) elements of 1 + P doubles (L, dL_p), leading dimension rows
+};
+
+int launch_gauss_sens_factor(const GaussSensSet *sets, const GaussSensJob *jobs, int njobs, int P, double *base, double *out,
+                             void *stream);
+int launch_gauss_sens_solve(const GaussSensSet *sets, const GaussSensJob *jobs, int njobs, int P, int nmax, double *out,
+                            void *stream);
+
 int launch_gauss_factor_sets(const GaussJobSet *d_sets, const GaussJob *d_jobs, int nsets, void *stream);
 int launch_gauss_sim_normals(const GaussSimProduct &p, void *stream);
 int launch_gauss_sim_product(const GaussSimProduct &p, void *stream);

@@ -12,8 +12,8 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .models import (MultiStateModel, MultiStateRouse, _REPLAY_GROUP_BYTES, _draw_normals, _missing_frames, _missing_is_none,
-                     _ragged_segments)
+from .models import (MultiStateModel, MultiStateRouse, _REPLAY_GROUP_BYTES, _draw_normals, _fisher_scoring, _fit_profiles,
+                     _log_chain_rule, _missing_frames, _missing_is_none, _ragged_segments)
 from .profiles import segments_from_states
 from .trajectory import Trajectory
 
@@ -213,6 +213,111 @@ class GenericGaussianModel(MultiStateModel):
         """ general batch: run-length encoded profiles over a set of trajectories """
         return _lib.gauss_logl_segments(self.handle(), self.trajset(trajs), seg_start, seg_state, traj_id)
 
+    # ------------------------------------------------------------------ parameter sensitivities and fit
+    _kalman_args = MultiStateRouse._kalman_args
+
+    def logL_sensitivities(self, profiles, trajs, dmsd=None, dmsd_inf=None, dmean=None, traj_id=None, fisher=True,
+                           scratch_bytes=0):
+        """
+        Log-likelihood of candidate profiles with its gradient and Fisher information with respect to P <= 4 parameters
+        (bild_gauss_logl_sensitivities: forward tangents of every window's Cholesky factor).
+
+        profiles, trajs, traj_id : as for `MultiStateRouse.logL_sensitivities`: expanded profiles of one trajectory, or
+            ``(seg_start, seg_state)`` over a list of trajectories with ``traj_id``
+        dmsd : (P, S, d, n_lags) derivatives of the MSD tables (n_lags = ``self.msd.shape[2]``), dmsd_inf and dmean :
+            (P, S, d) those of msd(inf) and of the means; None = zero.  The arrays given must agree on P.
+        fisher : return the Fisher information (innovations form: sum over the counted entries of every window of
+            dS_p dS_q / (2 S^2) + de_p de_q / S); its computation costs nothing extra, and logL does not depend on it
+        scratch_bytes : budget of the per-window factorisations of windows with a missing frame (0: the library's rule)
+
+        Returns (logL (n,), grad (n, P), fisher (n, P, P) or None); NaN rows where `logL_segments` gives NaN.
+        """
+        items, seg_start, seg_state, tid = self._kalman_args(profiles, trajs, traj_id)
+        S, d, n_lags = self.msd.shape
+        given = {}
+        for name, a, tail in (('dmsd', dmsd, (S, d, n_lags)), ('dmsd_inf', dmsd_inf, (S, d)), ('dmean', dmean, (S, d))):
+            if a is None:
+                continue
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim != len(tail) + 1 or a.shape[1:] != tail:
+                raise ValueError(f"{name} has shape {a.shape}, expected (P,) + {tail}")
+            given[name] = a
+        lens = {len(a) for a in given.values()}
+        if len(lens) > 1:
+            raise ValueError(f"derivative arrays disagree on the number of parameters: {sorted(lens)}")
+        P = lens.pop() if lens else 0
+        if P > 4:
+            raise _lib.BildAmdError(_lib.ERR_UNSUPPORTED, f"at most 4 parameters per call; {P} given")
+        for name, a in given.items():
+            if not np.all(np.isfinite(a)):
+                raise ValueError(f"{name} is not finite everywhere")
+        _, arrs = self._fingerprints(items)
+        for a in arrs:
+            if a.ndim != 2 or a.shape[1] != d:
+                raise ValueError(f"trajectory shape {a.shape} does not match the model's d = {d}")
+            if len(a) > self.max_T:
+                raise ValueError(f"trajectory of {len(a)} frames: GenericGaussianModel evaluates at most {self.max_T} "
+                                 f"(the GPU takes up to {MAX_T} frames, the MSD tables cover {n_lags} lags)")
+        if 'dmsd' in given:     # the library's tables end at lag Tmax = n_lags - 1, as the model handle's do
+            given['dmsd'] = given['dmsd'][..., :n_lags]
+        return _lib.gauss_logl_sensitivities(self.handle(), arrs, seg_start, seg_state, tid, P=P, fisher=fisher,
+                                             scratch_bytes=scratch_bytes, **given)
+
+    def _tables(self):
+        """ the tabulated arrays a fit differentiates: msd (S, d, n_lags), msd_inf and mean (S, d) """
+        return self.msd, self.msd_inf, self.mean
+
+    @classmethod
+    def fit(cls, trajs, profiles, family, start, derivatives=None, tol=1e-8, max_iter=50):
+        """
+        Maximum-likelihood fit of positive parameters theta on trajectories whose looping profiles are known, by Fisher
+        scoring in log theta with Levenberg damping (the stopping rule of `MultiStateRouse.fit`).
+
+        trajs : list of trajectories
+        profiles : one per trajectory (a `Loopingprofile`, a 1-d integer array, or ``(seg_start, seg_state)`` of shape
+            (n_traj, K1) for all of them), or a single state index: a constant profile
+        family : ``family(**theta)`` returns a ``state_spec``; every spec of the family must give MSD tables of one length
+        start : dict of starting values (at most 4 parameters, positive and finite)
+        derivatives : optional ``derivatives(**theta)`` -> (dmsd, dmsd_inf, dmean) with respect to theta, shaped as
+            `logL_sensitivities` takes them (None entries = zero).  Without it, central differences in log theta of the
+            tabulated msd, msd(inf) and means of the family's models (step 1e-5); the device part stays exact.
+        tol, max_iter : the fit stops when the Newton decrement g^T F^-1 g / 2 falls below ``tol``, or after ``max_iter``
+            device calls
+
+        Returns a `FitResult`: the fitted model, params, standard errors (inverse Fisher information at the optimum, by
+        the delta method from log theta), their covariance, logL, n_iter (device calls), converged and the history.
+        """
+        start = dict(start)
+        params = tuple(start)
+        if not params:
+            raise ValueError("nothing to fit: start is empty")
+        if len(params) > 4:
+            raise ValueError("at most 4 parameters")
+        theta = np.array([float(start[p]) for p in params])
+        if np.any(~np.isfinite(theta)) or np.any(theta <= 0):
+            raise ValueError(f"parameters must be positive and finite: {start}")
+        if tol <= 0 or max_iter < 1:
+            raise ValueError("need tol > 0 and max_iter >= 1")
+        items = list(trajs) if isinstance(trajs, (list, tuple)) else [trajs]
+        if not items:
+            raise ValueError("need at least one trajectory")
+        probe = cls(family(**dict(zip(params, theta))))
+        seg = _fit_profiles(profiles, [len(t) for t in items], probe.nStates)
+        tid = np.arange(len(items), dtype=np.int32)
+
+        def evaluate(th):
+            kw = dict(zip(params, th))
+            model = cls(family(**kw))
+            if derivatives is not None:
+                dmsd, dmsd_inf, dmean = derivatives(**kw)
+            else:
+                dmsd, dmsd_inf, dmean = _log_differences(cls, family, params, th)
+            logl, g, F = model.logL_sensitivities(seg, items, dmsd=dmsd, dmsd_inf=dmsd_inf, dmean=dmean, traj_id=tid)
+            g, F = _log_chain_rule(g, F, np.broadcast_to(th, g.shape))
+            return model, float(logl.sum()), g.sum(axis=0), F.sum(axis=0)
+
+        return _fisher_scoring(evaluate, theta, params, tol, max_iter)
+
     # ------------------------------------------------------------------ generative model
     def trajectory_from_loopingprofile(self, profile, missing_frames=None, rng=None):
         """
@@ -341,6 +446,30 @@ class GenericGaussianModel(MultiStateModel):
                                                               normals=z)
                 i0 = i1
         return [Trajectory(data[offs[i]:offs[i + 1]], loopingprofile=items[i]) for i in range(n)]
+
+
+_LOG_STEP = 1e-5
+
+
+def _log_differences(cls, family, params, theta, h=_LOG_STEP):
+    """
+    d(msd, msd_inf, mean) / d theta of the family's tabulated arrays by central differences in log theta (step h):
+    -> dmsd (P, S, d, n_lags), dmsd_inf, dmean (P, S, d)
+    """
+    out = None
+    for p in range(len(params)):
+        tabs = []
+        for sgn in (1.0, -1.0):
+            th = np.array(theta, dtype=np.float64)
+            th[p] *= np.exp(sgn * h)
+            tabs.append(cls(family(**dict(zip(params, th))))._tables())
+        if out is None:
+            out = [np.zeros((len(params),) + t.shape) for t in tabs[0]]
+        for o, hi, lo in zip(out, tabs[0], tabs[1]):
+            if hi.shape != o.shape[1:]:
+                raise ValueError("the family's models differ in the shape of their tables")
+            o[p] = (hi - lo) / (2 * h * theta[p])
+    return tuple(out)
 
 
 def normals_per_trajectory(ss_order, first_state, T):

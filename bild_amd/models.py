@@ -552,33 +552,7 @@ class MultiStateRouse(MultiStateModel):
             logl, g, F = model.logL_sensitivities(seg, items, params=params, traj_id=tid, log=True)
             return model, float(logl.sum()), g.sum(axis=0), F.sum(axis=0)
 
-        model, L, g, F = evaluate(theta)
-        history = [(dict(zip(params, theta)), L)]
-        mu, n_iter, converged = 0.0, 1, False
-        while True:
-            dec = _newton_decrement(g, F)
-            if dec < tol:
-                converged = True
-                break
-            if n_iter >= max_iter:
-                break
-            step = _damped_step(g, F, mu)
-            trial = theta * np.exp(step)
-            tm, tL, tg, tF = evaluate(trial)
-            n_iter += 1
-            if np.isfinite(tL) and tL > L:
-                theta, model, L, g, F = trial, tm, tL, tg, tF
-                history.append((dict(zip(params, theta)), L))
-                mu = 0.0 if mu <= 1e-3 else mu / 10.
-            else:
-                mu = 1e-3 if mu == 0.0 else mu * 10.
-                if mu > 1e12:
-                    break
-        cov_log = np.linalg.pinv(F)
-        cov = cov_log * np.outer(theta, theta)
-        se = np.sqrt(np.maximum(np.diag(cov), 0.))
-        return FitResult(model=model, params=dict(zip(params, theta)), se=dict(zip(params, se)), cov=cov, logL=L,
-                         n_iter=n_iter, converged=converged, history=history, names=params)
+        return _fisher_scoring(evaluate, theta, params, tol, max_iter)
 
     def _current_params(self, items, params):
         out = {'D': self._ctor['D'], 'k': self._ctor['k']}
@@ -739,7 +713,7 @@ class KalmanResult:
 
 class FitResult:
     """
-    `MultiStateRouse.fit`: ``model`` (at the fitted parameters), ``params`` and ``se`` (dicts by name), ``cov`` (P x P, in
+    `MultiStateRouse.fit`, `GenericGaussianModel.fit`: ``model`` (at the fitted parameters), ``params`` and ``se`` (dicts by name), ``cov`` (P x P, in
     the order of ``names``), ``logL`` (total at the optimum), ``n_iter`` (device calls), ``converged``, ``history``
     (accepted (params, logL) in order, the start first)
     """
@@ -770,6 +744,42 @@ def _damped_step(g, F, mu):
     """ the Levenberg-damped Fisher-scoring step (F + mu diag(F)) delta = g """
     A = F + mu * np.diag(np.diag(F))
     return np.linalg.lstsq(A, g, rcond=None)[0]
+
+
+def _fisher_scoring(evaluate, theta, params, tol, max_iter):
+    """
+    Fisher scoring in log theta with Levenberg damping, shared by the fits: ``evaluate(theta)`` -> (model, total logL,
+    gradient and Fisher information with respect to log theta).  Stops when the Newton decrement falls below ``tol``, after
+    ``max_iter`` evaluations, or when the damping exceeds 1e12; a step is accepted only if the logL rises.  -> `FitResult`
+    with standard errors from the inverse Fisher information by the delta method.
+    """
+    model, L, g, F = evaluate(theta)
+    history = [(dict(zip(params, theta)), L)]
+    mu, n_iter, converged = 0.0, 1, False
+    while True:
+        dec = _newton_decrement(g, F)
+        if dec < tol:
+            converged = True
+            break
+        if n_iter >= max_iter:
+            break
+        step = _damped_step(g, F, mu)
+        trial = theta * np.exp(step)
+        tm, tL, tg, tF = evaluate(trial)
+        n_iter += 1
+        if np.isfinite(tL) and tL > L:
+            theta, model, L, g, F = trial, tm, tL, tg, tF
+            history.append((dict(zip(params, theta)), L))
+            mu = 0.0 if mu <= 1e-3 else mu / 10.
+        else:
+            mu = 1e-3 if mu == 0.0 else mu * 10.
+            if mu > 1e12:
+                break
+    cov_log = np.linalg.pinv(F)
+    cov = cov_log * np.outer(theta, theta)
+    se = np.sqrt(np.maximum(np.diag(cov), 0.))
+    return FitResult(model=model, params=dict(zip(params, theta)), se=dict(zip(params, se)), cov=cov, logL=L,
+                     n_iter=n_iter, converged=converged, history=history, names=params)
 
 
 def _fit_profiles(profiles, lengths, n_states):

@@ -733,6 +733,35 @@ int bild_logl_sensitivities(const bild_model *m, const bild_trajset *ts, int64_t
                             const int32_t *seg_state, const int32_t *traj_id, int P, const bild_model_derivs *dm,
                             const double *ds2, double *logl, double *grad, double *fisher, int64_t scratch_bytes);
 
+/* ---------------------------------------------------------------- GenericGaussianModel sensitivities --
+ * The log-likelihood of candidate profiles under a GenericGaussianModel (the value of bild_gauss_logl_segments, to
+ * rounding) with its gradient and the innovations form of its Fisher information with respect to P <= 4 parameters
+ * theta_p, by forward tangents of the Cholesky factorisation of every window.  The caller gives the
+ * derivatives of the model arrays of bild_gauss_model_create, each P x (that array's shape), row-major, NULL = zero: dmsd
+ * P x S x d x (Tmax + 1), dmsd_inf and dmean P x S x d.  The trajectories are given directly, as bild_gauss_simulate takes
+ * them (n_traj, T, x: sum T x d, NaN = missing): no interval tables are built.  Segments and traj_id (may be NULL) as for
+ * bild_gauss_logl_segments.  Per candidate r:
+ *   logl[r]                       the log-likelihood (bild_gauss_logl_segments to rounding, not bit for bit)
+ *   grad[r * P + p]               d logl / d theta_p
+ *   fisher[(r * P + p) * P + q]   sum over the counted entries of every window of dS_p dS_q / (2 S^2) + de_p de_q / S, S the
+ *                                 innovation variance and e the innovation: symmetric, positive semi-definite, with the
+ *                                 Fisher information as its expectation
+ * NULL outputs are not written.  A candidate that bild_gauss_logl_segments gives NaN (a later ss_order-0 interval without a
+ * valid frame) gets NaN in all of its outputs; the others are untouched.  A candidate's outputs are a pure function of
+ * (model, derivatives, its trajectory, its profile): bit-identical whatever the batch, its order, duplicates, the chunking,
+ * and (logl) whatever P and whether fisher is NULL.  Windows are de-duplicated across the call; the factorisations of
+ * windows with a missing frame run in chunks within scratch_bytes (0: at most 1 GiB and a third of the free device memory).
+ * Before any device work: BILD_ERR_UNSUPPORTED for P > 4 and for a trajectory of more than 2048 frames, BILD_ERR_INVALID
+ * for a derivative that is not finite, a trajectory longer than the MSD tables (T - 1 > Tmax) and a bad segment row or
+ * traj_id.  Synchronous. */
+typedef struct bild_gauss_derivs {
+    const double *dmsd, *dmsd_inf, *dmean;
+} bild_gauss_derivs;
+int bild_gauss_logl_sensitivities(const bild_gauss_model *m, int n_traj, const int32_t *T, const double *x, int64_t n, int K1,
+                                  const int32_t *seg_start, const int32_t *seg_state, const int32_t *traj_id, int P,
+                                  const bild_gauss_derivs *dm, double *logl, double *grad, double *fisher,
+                                  int64_t scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
