@@ -152,6 +152,11 @@ _SIGNATURES = {
     # GenericGaussianModel log-likelihood sensitivities (gauss_sens.cpp)
     'bild_gauss_logl_sensitivities': (ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip,
                                                      ctypes.c_int, _vp, _dp, _dp, _dp, ctypes.c_int64]),
+    # GenericGaussianModel per-frame moments (gauss_kalman.cpp)
+    'bild_gauss_kalman_segments': (ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, _vp,
+                                                  ctypes.c_int64]),
+    'bild_gauss_kalman_mixture': (ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, _dp,
+                                                 _dp, _dp, ctypes.c_int64]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -675,6 +680,59 @@ def gauss_logl_sensitivities(model, trajs, seg_start, seg_state, traj_id=None, d
                                               dptr(g) if g.size else None, dptr(F) if F is not None and F.size else None,
                                               int(scratch_bytes)))
     return logl, g, F
+
+
+GAUSS_KALMAN_OUTPUTS = ('terms', 'pred_mean', 'pred_var', 'smooth_mean', 'smooth_var', 'innov')
+
+
+def gauss_kalman_segments(model, trajs, seg_start, seg_state, traj_id=None, outputs=GAUSS_KALMAN_OUTPUTS, T_max=None,
+                          scratch_bytes=0):
+    """
+    per-frame moments of GenericGaussianModel candidates (bild_gauss_kalman_segments) of the model handle ``model``: trajs a
+    list of (T, d) arrays, segments (n, K1); a dict of the requested outputs (names of KALMAN_OUTPUTS), each (n, T_max, d)
+    float64, T_max defaulting to the longest trajectory
+    """
+    seg_start, seg_state = i32(seg_start), i32(seg_state)
+    n, K1 = seg_start.shape
+    assert seg_state.shape == (n, K1)
+    tid = None if traj_id is None else i32(traj_id)
+    assert tid is None or tid.shape == (n,)
+    arrs = [f64(t) for t in trajs]
+    T = i32([a.shape[0] for a in arrs])
+    x = f64(np.concatenate(arrs, axis=0))
+    if T_max is None:
+        T_max = int(np.max(T))
+    res = {}
+    spec = KalmanOut(T_max=int(T_max))
+    for name in outputs:
+        if name not in KALMAN_OUTPUTS:
+            raise ValueError(f"unknown output {name!r}")
+        res[name] = np.empty((n, T_max, model.d), dtype=np.float64)
+        setattr(spec, name, aptr(res[name]) if res[name].size else None)
+    check(lib().bild_gauss_kalman_segments(model._h, len(arrs), iptr(T), dptr(x), n, K1, iptr(seg_start), iptr(seg_state),
+                                           iptr(tid), ctypes.byref(spec), int(scratch_bytes)))
+    return res
+
+
+def gauss_kalman_mixture(model, trajs, seg_start, seg_state, log_weights, traj_id=None, scratch_bytes=0):
+    """
+    posterior mixture of the smoothed coordinate per trajectory (bild_gauss_kalman_mixture): (mean, var), each
+    (n_traj, T_max, d), T_max the longest trajectory
+    """
+    seg_start, seg_state = i32(seg_start), i32(seg_state)
+    n, K1 = seg_start.shape
+    assert seg_state.shape == (n, K1)
+    lw = f64(log_weights).reshape(-1)
+    assert lw.shape == (n,)
+    tid = None if traj_id is None else i32(traj_id)
+    arrs = [f64(t) for t in trajs]
+    T = i32([a.shape[0] for a in arrs])
+    x = f64(np.concatenate(arrs, axis=0))
+    mean = np.empty((len(arrs), int(np.max(T)), model.d), dtype=np.float64)
+    var = np.empty_like(mean)
+    check(lib().bild_gauss_kalman_mixture(model._h, len(arrs), iptr(T), dptr(x), n, K1, iptr(seg_start), iptr(seg_state),
+                                          iptr(tid), dptr(lw), dptr(mean), dptr(var), int(scratch_bytes)))
+    return mean, var
 
 
 def prefix_info(ts):

@@ -879,8 +879,9 @@ class FixedkSampler:
 
     def posterior_distance(self):
         """
-        (mean, var), each (T, d): the smoothed distance y_t = w.x_t averaged over the pooled samples' profiles with the
-        weights `log_marginal_posterior` uses (law of total variance; MultiStateRouse.kalman_mixture).  MultiStateRouse only.
+        (mean, var), each (T, d): the smoothed track averaged over the pooled samples' profiles with the weights
+        `log_marginal_posterior` uses (law of total variance; the model's ``kalman_mixture``): the distance y_t = w.x_t
+        for a MultiStateRouse, the observed coordinate for a GenericGaussianModel.
         """
         seg_start, seg_state, log_weights = self._posterior_segments()
         mean, var = self.model.kalman_mixture((seg_start, seg_state), [self.traj], log_weights)
@@ -888,9 +889,11 @@ class FixedkSampler:
 
     def _posterior_segments(self):
         """ the pooled samples as run-length segments, with their log-weights (those of log_marginal_posterior) """
+        from .gauss import GenericGaussianModel
         from .models import MultiStateRouse
-        if not isinstance(self.model, MultiStateRouse):
-            raise TypeError(f"posterior distances need a MultiStateRouse model, not {type(self.model).__name__}")
+        if not isinstance(self.model, (MultiStateRouse, GenericGaussianModel)):
+            raise TypeError(f"posterior distances need a MultiStateRouse or GenericGaussianModel, not "
+                            f"{type(self.model).__name__}")
         pooled = dict(self._arr, ss=self._pool['ss'], thetas=self._pool['thetas'])
         log_weights = pooled['log_weights'] if 'log_weights' in pooled else pooled['logLs']
         seg_start, seg_state = segments_from_st(pooled['ss'], np.asarray(pooled['thetas']), len(self.traj))

@@ -446,9 +446,9 @@ class SamplingResults:
 
     def posterior_distance(self, dE=None):
         """
-        (mean, var), each (T, d): the smoothed distance w.x averaged over the posterior of profiles, as
-        `log_marginal_posterior` averages the states -- the sampler at `best_k` by default, ``dE='average'``: all k,
-        each sampler's normalised weights times its evidence.  MultiStateRouse only.
+        (mean, var), each (T, d): the smoothed track (the distance w.x for a MultiStateRouse, the observed coordinate for a
+        GenericGaussianModel) averaged over the posterior of profiles, as `log_marginal_posterior` averages the states --
+        the sampler at `best_k` by default, ``dE='average'``: all k, each sampler's normalised weights times its evidence.
         """
         seg_start, seg_state, log_weights = self._posterior_parts(dE)
         mean, var = self.model.kalman_mixture((seg_start, seg_state), [self.traj], log_weights)

@@ -59,6 +59,12 @@ int launch_gauss_sim_assemble(const GaussSimAssemble &, void *) { return 1; }
 int launch_gauss_sens_factor(const GaussSensSet *, const GaussSensJob *, int, int, double *, double *, void *) { return 1; }
 int launch_gauss_sens_solve(const GaussSensSet *, const GaussSensJob *, int, int, int, double *, void *) { return 1; }
 } // namespace bild
+#include "gauss_kalman.h"
+namespace bild {
+int launch_gauss_kal_factor(const GaussKalSet *, const GaussKalJob *, int, double *, double *, void *) { return 1; }
+int launch_gauss_kal_solve(const GaussKalSet *, const GaussKalJob *, int, int, double *, void *) { return 1; }
+int launch_gauss_kal_scatter(const GaussKalScatter &, void *) { return 1; }
+} // namespace bild
 #include "exchange.h"
 namespace bild {
 int launch_exchange(const ExParams &, void *) { return 1; }

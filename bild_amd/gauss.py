@@ -12,8 +12,8 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .models import (MultiStateModel, MultiStateRouse, _REPLAY_GROUP_BYTES, _draw_normals, _fisher_scoring, _fit_profiles,
-                     _log_chain_rule, _missing_frames, _missing_is_none, _ragged_segments)
+from .models import (KalmanResult, MultiStateModel, MultiStateRouse, _REPLAY_GROUP_BYTES, _draw_normals, _fisher_scoring,
+                     _fit_profiles, _log_chain_rule, _missing_frames, _missing_is_none, _ragged_segments)
 from .profiles import segments_from_states
 from .trajectory import Trajectory
 
@@ -251,17 +251,77 @@ class GenericGaussianModel(MultiStateModel):
         for name, a in given.items():
             if not np.all(np.isfinite(a)):
                 raise ValueError(f"{name} is not finite everywhere")
-        _, arrs = self._fingerprints(items)
-        for a in arrs:
-            if a.ndim != 2 or a.shape[1] != d:
-                raise ValueError(f"trajectory shape {a.shape} does not match the model's d = {d}")
-            if len(a) > self.max_T:
-                raise ValueError(f"trajectory of {len(a)} frames: GenericGaussianModel evaluates at most {self.max_T} "
-                                 f"(the GPU takes up to {MAX_T} frames, the MSD tables cover {n_lags} lags)")
+        arrs = self._direct_arrays(items)
         if 'dmsd' in given:     # the library's tables end at lag Tmax = n_lags - 1, as the model handle's do
             given['dmsd'] = given['dmsd'][..., :n_lags]
         return _lib.gauss_logl_sensitivities(self.handle(), arrs, seg_start, seg_state, tid, P=P, fisher=fisher,
                                              scratch_bytes=scratch_bytes, **given)
+
+    def _direct_arrays(self, items):
+        """ the (T, d) arrays of trajectories that a call takes directly (no trajectory set), checked on the host """
+        _, arrs = self._fingerprints(items)
+        for a in arrs:
+            if a.ndim != 2 or a.shape[1] != self.d:
+                raise ValueError(f"trajectory shape {a.shape} does not match the model's d = {self.d}")
+            if len(a) > self.max_T:
+                raise ValueError(f"trajectory of {len(a)} frames: GenericGaussianModel evaluates at most {self.max_T} "
+                                 f"(the GPU takes up to {MAX_T} frames, the MSD tables cover {self.msd.shape[2]} lags)")
+        return arrs
+
+    # ------------------------------------------------------------------ per-frame moments
+    def kalman(self, profiles, trajs, traj_id=None, outputs=('smooth',), scratch_bytes=0):
+        """
+        Per-frame moments of candidate profiles (bild_gauss_kalman_segments), from the Cholesky
+        factor of every window of the likelihood.  Each frame is taken from the window of the interval that contains it.
+
+        profiles, trajs, traj_id : as for `MultiStateRouse.kalman`
+        outputs : subset of 'terms', 'pred', 'smooth', 'innov' ('filt' is not offered: the model has no filter)
+        scratch_bytes : budget of the window factorisations and of one chunk of outputs (0: the library's rule)
+
+        Returns a `KalmanResult` with arrays (n, T_max, d), NaN behind a trajectory's own length:
+
+        * ``terms``: the log-likelihood term of each entry the likelihood counts, at its frame (the frame of the value,
+          ss_order 0, or the end of the increment, ss_order 1), 0.0 elsewhere; summed, `logL_segments` to rounding;
+        * ``pred_mean``, ``pred_var``: the observed coordinate given the earlier entries of its window, at counted frames;
+        * ``innov``: the standardised innovation there (NaN elsewhere, as ``pred_*``);
+        * ``smooth_mean``, ``smooth_var``: the coordinate given every valid frame of its window -- the data and 0 at a
+          valid frame, the Gaussian conditional at a missing one (NaN for an ss_order-1 frame before the window's first
+          valid frame).  The MSDs contain the localization noise and the model does not split it off, so these are
+          moments of the *observed* coordinate, not of a noise-free one as `MultiStateRouse.kalman` gives.
+
+        A candidate that `logL_segments` gives NaN (a later ss_order-0 interval without a valid frame) is NaN over that
+        interval and dimension.  Argument errors are raised before any device work.
+        """
+        outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+        for o in outputs:
+            if o == 'filt':
+                raise ValueError("GenericGaussianModel has no filtered moments ('filt'); choose from 'terms', 'pred', "
+                                 "'smooth', 'innov'")
+            if o not in KalmanResult.GROUPS:
+                raise ValueError(f"unknown output {o!r}; choose from {sorted(KalmanResult.GROUPS)}")
+        items, seg_start, seg_state, tid = self._kalman_args(profiles, trajs, traj_id)
+        arrs = self._direct_arrays(items)
+        names = [name for o in outputs for name in KalmanResult.GROUPS[o]]
+        res = _lib.gauss_kalman_segments(self.handle(), arrs, seg_start, seg_state, tid, outputs=names,
+                                         scratch_bytes=scratch_bytes)
+        return KalmanResult(res)
+
+    def kalman_mixture(self, profiles, trajs, log_weights, traj_id=None, scratch_bytes=0):
+        """
+        Posterior mixture of the smoothed coordinate over weighted candidates (bild_gauss_kalman_mixture): per trajectory
+        of ``trajs``, the candidates on it weighted by exp(log_weights), normalised within the trajectory (law of total
+        variance).  Arguments as for `kalman`.  -> (mean, var), each (n_traj, T_max, d); NaN for a trajectory without
+        candidates of finite weight.  At a valid frame the mean is the data and the variance 0.
+        """
+        items, seg_start, seg_state, tid = self._kalman_args(profiles, trajs, traj_id)
+        log_weights = np.asarray(log_weights, dtype=np.float64).reshape(-1)
+        if log_weights.shape != (len(seg_start),):
+            raise ValueError(f"{len(log_weights)} log-weights for {len(seg_start)} candidates")
+        if np.any(np.isnan(log_weights)) or np.any(log_weights == np.inf):
+            raise ValueError("log-weights must be finite or -inf (NaN or +inf given)")
+        arrs = self._direct_arrays(items)
+        return _lib.gauss_kalman_mixture(self.handle(), arrs, seg_start, seg_state, log_weights, tid,
+                                         scratch_bytes=scratch_bytes)
 
     def _tables(self):
         """ the tabulated arrays a fit differentiates: msd (S, d, n_lags), msd_inf and mean (S, d) """

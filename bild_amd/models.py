@@ -694,7 +694,8 @@ class MultiStateRouse(MultiStateModel):
 
 class KalmanResult:
     """
-    Per-frame moments of `MultiStateRouse.kalman`, each (n, T_max, d) float64 or None when not requested:
+    Per-frame moments of `MultiStateRouse.kalman` and `GenericGaussianModel.kalman` (which offers no ``filt_*``; its
+    ``smooth_*`` are moments of the observed coordinate), each (n, T_max, d) float64 or None when not requested:
     ``terms`` (log-likelihood of each observation, 0.0 on missing frames), ``pred_mean`` / ``pred_var`` (the observation
     given the frames before), ``filt_mean`` / ``filt_var`` and ``smooth_mean`` / ``smooth_var`` (the noise-free y = w.x
     given the frames up to t / all frames), ``innov`` (standardised one-step-ahead innovations, NaN on missing frames).

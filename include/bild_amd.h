@@ -762,6 +762,42 @@ int bild_gauss_logl_sensitivities(const bild_gauss_model *m, int n_traj, const i
                                   const bild_gauss_derivs *dm, double *logl, double *grad, double *fisher,
                                   int64_t scratch_bytes);
 
+/* ---------------------------------------------------------------- GenericGaussianModel moments --------
+ * Per-frame moments of candidate profiles under a GenericGaussianModel (GenericGaussianModel.kalman; DESIGN.md section
+ * 16), from the Cholesky factorisation of every window of the likelihood.  Trajectories, segments and traj_id as for
+ * bild_gauss_logl_sensitivities; outputs as for bild_kalman_segments (n x T_max x d each, NULL = not computed, NaN behind
+ * a candidate's own T), each frame t of dimension k taken from the window of the interval that contains t.  With the
+ * window's data vector y (entry j at its valid frame v_j, ss_order 0, or at v_{j+1}, the increment v_j -> v_{j+1},
+ * ss_order 1), L L^T its covariance and z = L^-1 y:
+ *   terms                 -(log L_jj + z_j^2 / 2 + log(2 pi) / 2) at the frame of an entry the likelihood counts, 0.0
+ *                         elsewhere (summed: bild_gauss_logl_segments to rounding)
+ *   pred_mean, pred_var   the observed coordinate given the earlier entries of its window, at counted frames (else NaN)
+ *   innov                 z_j at counted frames (else NaN)
+ *   smooth_mean, smooth_var   the observed coordinate given every valid frame of its window: the data and 0 at a valid
+ *                         frame; the Gaussian conditional at a missing one (NaN for an ss_order-1 frame before the
+ *                         window's first valid frame).  The MSDs include the localization noise, so these are moments of
+ *                         the observed coordinate, not of a noise-free one.
+ * filt_mean and filt_var must be NULL (the model has no filter): BILD_ERR_INVALID.  A later ss_order-0 window without a
+ * valid frame (bild_gauss_logl_segments: NaN) gives NaN over its frames and dimension in every output.  A candidate's
+ * outputs are a pure function of (model, its trajectory, its profile): bit-identical whatever the batch, its order,
+ * duplicates and the chunking.  Windows are de-duplicated across the call; the factorisations of windows with a missing
+ * frame, and the outputs, run in chunks within scratch_bytes (0: at most 1 GiB and a third of the free device memory).
+ * Before any device work: the refusals of bild_gauss_logl_sensitivities, T_max shorter than a candidate's trajectory and
+ * a negative scratch_bytes.  Synchronous. */
+int bild_gauss_kalman_segments(const bild_gauss_model *m, int n_traj, const int32_t *T, const double *x, int64_t n, int K1,
+                               const int32_t *seg_start, const int32_t *seg_state, const int32_t *traj_id,
+                               const bild_kalman_out *out, int64_t scratch_bytes);
+/* The posterior mixture of the smoothed coordinate over the candidates of each trajectory, weights exp(log_weights)
+ * normalised within the trajectory, as bild_kalman_mixture forms it: mean = sum w m / W, var = sum w v / W +
+ * sum w (m - mean)^2 / W, accumulated around the smoothed track of the trajectory's highest-weight candidate (the first of
+ * them) in fixed blocks of 64 candidates in index order, weight 0 skipped; so the result does not depend on the chunking,
+ * and at a valid frame the mean is the data and the variance 0.  mean, var: n_traj x T_max x d, T_max the longest
+ * trajectory; NaN behind a trajectory's T and for a trajectory without candidates or with all log-weights -inf.  NaN or
+ * +inf log-weights: BILD_ERR_INVALID, before any device work. */
+int bild_gauss_kalman_mixture(const bild_gauss_model *m, int n_traj, const int32_t *T, const double *x, int64_t n, int K1,
+                              const int32_t *seg_start, const int32_t *seg_state, const int32_t *traj_id,
+                              const double *log_weights, double *mean, double *var, int64_t scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
