@@ -10,10 +10,11 @@ One hot path, behind the reference's own interfaces:
 both evaluated by hand-written HIP kernels for gfx950 through the C ABI declared in
 ``include/bild_amd.h`` (``bild_amd/libbild_amd.so``).  There is no CPU fallback.
 """
-from . import rouse, profiles, util, trajectory, models, gauss, amis, choicesampler, core, postproc  # noqa: F401
+from . import rouse, profiles, util, trajectory, models, gauss, amis, choicesampler, core, postproc, exact  # noqa: F401
 from .core import sample, sample_many, SamplingResults, posterior_distances  # noqa: F401
 from .models import MultiStateModel, MultiStateRouse, FactorizedModel, KalmanResult, FitResult  # noqa: F401
 from .gauss import GenericGaussianModel  # noqa: F401
+from .exact import exact_evidence, ExactResult  # noqa: F401
 from .amis import FixedkSampler, Dirichlet, CFC  # noqa: F401
 from .profiles import Loopingprofile  # noqa: F401
 from .trajectory import Trajectory  # noqa: F401

@@ -157,6 +157,11 @@ _SIGNATURES = {
                                                   ctypes.c_int64]),
     'bild_gauss_kalman_mixture': (ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, ctypes.c_int64, ctypes.c_int, _ip, _ip, _ip, _dp,
                                                  _dp, _dp, ctypes.c_int64]),
+    # exact evidence by enumeration (exact.cpp)
+    'bild_exact_count': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(ctypes.c_double)]),
+    'bild_exact_evidence': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_int64, ctypes.c_int, ctypes.c_uint,
+                                           _vp]),
+    'bild_gauss_exact_evidence': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_int64, ctypes.c_int, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1201,3 +1206,46 @@ def interval_marginals(seg_start, seg_state, w, n, T):
     if code != OK:
         raise BildAmdError(code, "bild_interval_marginals failed")
     return post
+
+
+class ExactOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'kl', 'map_logl', 'map_seg_start', 'map_seg_state', 'n_nan',
+                                                      'log_post')]
+
+
+def _transitions_u8(transitions, S):
+    tr = np.ascontiguousarray(np.asarray(transitions, dtype=bool), dtype=np.uint8)
+    if tr.shape != (S, S):
+        raise ValueError(f"transitions of shape {tr.shape}; the model has {S} states: ({S}, {S}) expected")
+    return tr
+
+
+def exact_count(T, k, transitions):
+    """ number of profiles of k switches on a trajectory of T frames (bild_exact_count; host only) """
+    tr = _transitions_u8(transitions, np.asarray(transitions).shape[0])
+    n = ctypes.c_double(0)
+    check(lib().bild_exact_count(int(T), int(k), tr.shape[0], aptr(tr), ctypes.byref(n)))
+    return n.value
+
+
+def exact_evidence(model, ts, k, transitions, marginals=True, max_profiles=2 ** 32, scratch_bytes=0, gauss=False, path='auto'):
+    """
+    exact evidence of every trajectory of the set (bild_exact_evidence / bild_gauss_exact_evidence): a dict of
+    logev, kl, map_logl (n_traj,), map_seg_start, map_seg_state (n_traj, k + 1) int32, n_nan (n_traj,) int64 and
+    log_post (n_traj, S, T_max) or None; T_max is the set's longest trajectory
+    """
+    tr = _transitions_u8(transitions, model.S)
+    n, K1 = ts.n_traj, int(k) + 1
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty(n), 'kl': np.empty(n), 'map_logl': np.empty(n),
+           'map_seg_start': np.empty((n, K1), dtype=np.int32), 'map_seg_state': np.empty((n, K1), dtype=np.int32),
+           'n_nan': np.empty(n, dtype=np.int64),
+           'log_post': np.empty((n, model.S, T_max)) if marginals else None}
+    spec = ExactOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
+    if gauss:
+        check(lib().bild_gauss_exact_evidence(model._h, ts._h, int(k), aptr(tr), float(max_profiles), int(scratch_bytes), T_max,
+                                              ctypes.byref(spec)))
+    else:
+        check(lib().bild_exact_evidence(model._h, ts._h, int(k), aptr(tr), float(max_profiles), int(scratch_bytes), T_max,
+                                        _flags(path), ctypes.byref(spec)))
+    return res

@@ -5,6 +5,7 @@
 
 #include "likelihood.h"
 #include "gauss.h"
+#include "internal.h"
 
 struct bild_gauss_trajset {
     const bild_gauss_model *model = nullptr;
@@ -243,6 +244,33 @@ int run_walk(bild_gauss_trajset *ts, GaussWalk &w, bool st, std::initializer_lis
 }
 
 } // namespace
+
+int bild::internal_gauss_set_lengths(const bild_gauss_model *m, const bild_gauss_trajset *ts, int *n_traj, const int **T)
+{
+    if (!m || !ts) return fail(BILD_ERR_INVALID, "NULL handle");
+    if (ts->model != m) return fail(BILD_ERR_INVALID, "trajectory set belongs to a different model");
+    *n_traj = ts->n_traj;
+    *T = ts->T.data();
+    return BILD_OK;
+}
+
+int bild::internal_gauss_walk_resident(const bild_gauss_model *m, const bild_gauss_trajset *ts, int64_t n, int K1, const int32_t *d_seg_start,
+                                       const int32_t *d_seg_state, const int32_t *d_traj_id, double *d_out, void *stream)
+{
+    if (!m || !ts || ts->model != m || n < 0 || K1 < 1 || !d_seg_start || !d_seg_state || !d_out)
+        return fail(BILD_ERR_INVALID, "internal_gauss_walk_resident: bad arguments");
+    GaussWalk w{};
+    w.trajs = ts->d_trajs;
+    w.seg_start = d_seg_start;
+    w.seg_state = d_seg_state;
+    w.traj_id = d_traj_id;
+    w.out = d_out;
+    w.n = n;
+    w.K1 = K1;
+    w.S = m->S;
+    if (launch_gauss_walk(w, false, stream)) return fail(BILD_ERR_HIP, "launch of the walk kernel failed");
+    return BILD_OK;
+}
 
 extern "C" {
 

@@ -4,6 +4,8 @@
 
 struct bild_model;
 struct bild_trajset;
+struct bild_gauss_model;
+struct bild_gauss_trajset;
 
 namespace bild {
 
@@ -16,5 +18,12 @@ int internal_logl_st_resident(const bild_model *m, const bild_trajset *ts, int64
 
 // the model's own stream (a hipStream_t): device copies of the model are made on first use; null on failure
 void *internal_model_stream(const bild_model *m);
+
+// GenericGaussianModel (gauss.cpp): the number of trajectories of a set and their frames (valid while the set lives)
+int internal_gauss_set_lengths(const bild_gauss_model *m, const bild_gauss_trajset *ts, int *n_traj, const int **T);
+// the walk (gauss_walk_kernel<false>) over segment rows that are ALREADY in HBM, results to d_out (device, n doubles), on
+// `stream` (a hipStream_t); nothing is waited for.  The set's tables are complete when it is created: any stream may read them.
+int internal_gauss_walk_resident(const bild_gauss_model *m, const bild_gauss_trajset *ts, int64_t n, int K1, const int32_t *d_seg_start,
+                                 const int32_t *d_seg_state, const int32_t *d_traj_id, double *d_out, void *stream);
 
 } // namespace bild

@@ -798,6 +798,52 @@ int bild_gauss_kalman_mixture(const bild_gauss_model *m, int n_traj, const int32
                               const int32_t *seg_start, const int32_t *seg_state, const int32_t *traj_id,
                               const double *log_weights, double *mean, double *var, int64_t scratch_bytes);
 
+/* ---------------------------------------------------------------- exact evidence by enumeration --------
+ * For a fixed number k of switches, every profile of a trajectory of T frames: a switch combination c_1 < ... < c_k from
+ * {1, ..., T - 1} (a segment starting at each c_i) and a valid trace, k + 1 states whose consecutive pairs transitions
+ * (S x S, row-major, 0 / 1) allows.  Traces are the outer index in FixedkSampler's CFC.full_sample order, combinations
+ * the inner one in itertools.combinations order: the order in which FixedkSampler.fix_exhaustive pools them.  Under the
+ * uniform prior over these profiles, per trajectory:
+ *   logev      log mean exp(logL): top = the largest logL, log(mean exp(logL - top)) + top
+ *   kl         mean(logL exp(logL - top)) / mean(exp(logL - top)) - logev (KL of the posterior from the prior)
+ *   map_*      the profile of largest logL, the first in the order above among equal maxima, as segments (k + 1 each),
+ *              and its logL -- the value the likelihood call gives for it
+ *   n_nan      candidates whose logL is NaN (GenericGaussianModel: DESIGN.md section 10).  With any of them logev, kl and
+ *              the marginals are NaN, as on the host; the MAP is taken among the others.
+ *   log_post   (NULL: not computed) the normalised log marginal posterior of the state at each frame, S x T_max per
+ *              trajectory, NaN behind its T: log(sum of exp(logL - top) over the profiles in state s at frame t) minus the
+ *              log of that sum over s -- sums of non-negative terms only.
+ * A candidate with logL = -inf weighs 0 and adds 0 to kl's numerator (the host's formula gives NaN there).  A trajectory
+ * with T - 1 < k has no profiles: logev -inf, kl NaN, map segments -1, map_logl NaN, log_post NaN; the others are computed
+ * as usual.  Results are bit-identical across calls, the order of the set's trajectories, a trajectory alone or in a
+ * batch, and scratch_bytes (the work is reduced in blocks of 4096 consecutive profiles of one trajectory and folded in
+ * block order) -- given bit-identical log-likelihoods: MultiStateRouse gives those on one set (see "REPRODUCIBILITY
+ * CONTRACT" above; the same trajectory on another set agrees to rounding).
+ * Refused before any device work: k outside 0 .. 15 (BILD_ERR_UNSUPPORTED), a transitions entry other than 0 / 1, T_max
+ * shorter than a trajectory of the set, a negative scratch_bytes (BILD_ERR_INVALID); more profiles in all than
+ * max_profiles, 2^53 or more for one trajectory, more than 2^26 valid traces, and with log_post S x T above 8192 for a
+ * trajectory (the LDS accumulators of a block) (BILD_ERR_UNSUPPORTED, the count in the message).  Chunks of whole blocks
+ * run within scratch_bytes (0: at most 1 GiB and a third of the free device memory; at least one block).  Synchronous. */
+
+/* host only, no device: C(T - 1, k) x (valid traces of k switches), as a double (exact below 2^53); T >= 1 */
+int bild_exact_count(int T, int k, int S, const uint8_t *transitions, double *n_profiles);
+
+typedef struct bild_exact_out {
+    double *logev, *kl, *map_logl;          /* n_traj each */
+    int32_t *map_seg_start, *map_seg_state; /* n_traj x (k + 1) */
+    int64_t *n_nan;                         /* n_traj */
+    double *log_post;                       /* n_traj x S x T_max, NULL = marginals not computed */
+} bild_exact_out;                           /* every pointer may be NULL: not written */
+
+/* MultiStateRouse: the profiles are evaluated by bild_logl_segments_device on the model's stream (evaluation path: the
+ * low 4 bits of flags).  A set that has not been evaluated on yet and whose declaration (bild_trajset_expect) is below the
+ * call's count -- or that has none and sees 1e8 profiles or more -- is declared for the count. */
+int bild_exact_evidence(const bild_model *m, const bild_trajset *ts, int k, const uint8_t *transitions, double max_profiles,
+                        int64_t scratch_bytes, int T_max, unsigned flags, bild_exact_out *out);
+/* GenericGaussianModel: the walk of bild_gauss_logl_segments over the rows in HBM */
+int bild_gauss_exact_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k, const uint8_t *transitions,
+                              double max_profiles, int64_t scratch_bytes, int T_max, bild_exact_out *out);
+
 #ifdef __cplusplus
 }
 #endif
