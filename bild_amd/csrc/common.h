@@ -182,6 +182,23 @@ struct WalkParams {
     int32_t debug;                  // timing experiments only (BILD_WALK_DEBUG; wrong results): 1 no pair loads, 2 no append, 4 no loads at all
 };
 int launch_walk(const WalkParams &p, void *stream, void *ev_start = nullptr, void *ev_stop = nullptr);
+
+// The one-launch path (kernels.hip: logl_one_kernel): the table walk and the listed frame loop in ONE grid.  Workgroup b walks the
+// tasks [b * slice, (b + 1) * slice) of the batch, slice = ceil(tasks / grid) <= kOneSlice, and hands the tasks its walk could not
+// finish to its own waves through LDS: this record, behind the walk plans of the rows (the LDS areas of the two-kernel path).
+constexpr int kOneSlice = 64;
+// largest batch (tasks = candidates x d*) the walk and the listed frame loop share one launch for (launch.cpp: launch_batch)
+constexpr int64_t kOneLaunchMaxTasks = 32768;
+// ... and the longest lists: at k = 8 a third of the batch is listed, a workgroup then holds more tasks than row pairs and runs the
+// one-row frame, where the two-kernel path deals the whole list over the grid's row pairs (10k x k = 8: 76.9 -> 91.5 us per step)
+constexpr int kOneLaunchMaxK1 = 5;
+struct OneHand {
+    int32_t cnt[4];              // listed tasks per wave (the slice is spread over the waves: position j on wave j % 4)
+    int32_t n, pad;              // listed tasks of the workgroup
+    int32_t task[kOneSlice];     // position q of the deal (heaviest first) -> task
+    int32_t reg_task[kOneSlice]; // the listed tasks in wave / lane order, with ...
+    int32_t reg_w[kOneSlice];    // ... their expected frames (walk.hip: the bucket estimate)
+};
 int launch_tail(const TrajDesc *d_trajs, int n_traj, int S, int NP, int d, int dstar_max, const double *d_states, const double *d_prefix,
                 const int64_t *d_first, int64_t total, double *d_gain, double *d_tail_g, void *stream);
 int launch_mark_refused_rows(const int32_t *seg_start, int K1, int64_t n, double *out, void *stream);
@@ -216,6 +233,9 @@ constexpr int kWalkDoubles = 3 * kSegLds;
 // (ev_start / ev_stop: hipEvent_t attached to the dispatch of a timed launch, or null)
 int launch_logl(const Geometry &g, int mode, const KParams &p, int grid, size_t lds_bytes, void *stream, void *ev_start = nullptr,
                 void *ev_stop = nullptr);
+// geometry 23 only (hipErrorInvalidValue otherwise); lds_bytes: the frame loop's LDS with the walk plans, + sizeof(OneHand)
+int launch_logl_one(const Geometry &g, const KParams &p, const WalkParams &w, int grid, size_t lds_bytes, void *stream, void *ev_start,
+                    void *ev_stop);
 int launch_reduce_partials(const double *partial, double *out, int64_t n, int dstar_max, void *stream);
 int launch_prefix_L(const TrajDesc *d_trajs, int n_traj, int S, int NP, int dstar_max, int Tmax, double *d_prefix, double *d_prefix_L, void *stream);
 // d_err: 2 ints (verdict, a sample that shows it) followed, when `order` is given, by n hit counters; zeroed by the caller

@@ -57,6 +57,7 @@ void load(Config &c)
     flag("BILD_NO_LISTED_GEOMETRY", c.no_listed_geometry);
     flag("BILD_DENSE_VALU", c.dense_valu);
     flag("BILD_NO_FUSED_LAUNCH", c.no_fused_launch);
+    flag("BILD_NO_ONE_LAUNCH", c.no_one_launch);
     num("BILD_GEOM", c.geom);
     num("BILD_WIDE_THREADS", c.wide_threads);
     num("BILD_WALK_DEBUG", c.walk_debug);

@@ -31,6 +31,7 @@ struct Config {
     bool no_listed_geometry = false; // BILD_NO_LISTED_GEOMETRY
     bool dense_valu = false;         // BILD_DENSE_VALU         dense path on the vector pipe
     bool no_fused_launch = false;    // BILD_NO_FUSED_LAUNCH    walk and frame loop as two launches (A/B against the fused grid)
+    bool no_one_launch = false;      // BILD_NO_ONE_LAUNCH      walk and listed frame loop as two kernels (A/B against logl_one_kernel)
     int geom = -1;                   // BILD_GEOM               force a geometry id
     int wide_threads = 0;            // BILD_WIDE_THREADS       256 / 512 / 1024
     int walk_debug = 0;              // BILD_WALK_DEBUG

@@ -45,6 +45,7 @@
 
 #include "config.h"
 #include "common.h"
+#include "walk_task.h"
 
 // expected frames of a wave's busiest row from which it asks for issue priority 1 / 2 / 3 (logl_kernel, "wave priority")
 #ifndef BILD_PRIO_T1
@@ -288,8 +289,12 @@ __device__ __forceinline__ void matvec_to_lds(XPtr X, const Cols<NP, CPL> &in, d
 // row holds the even entries of column j of [C | M], the odd row the odd ones -- half the predict, dot and rank-1 instructions of
 // a frame.  Everything else (prologue, events, epilogue) runs in both rows alike on whole columns, unpacked from the halves at an
 // event and packed again behind it; both rows then hold the same bits, so they take the same branches.
-template <int NP, int CPL, int G, int W, int OCC, int LAY, int MODE, int FLAVOR, bool DUMP, bool JUMP, bool BUILD, bool PAIR = false>
-__device__ __forceinline__ void logl_body(const KParams &p)
+// ONE: the listed frame loop of the one-launch path (logl_one_kernel): the workgroup's own table walk (walk_one) has left its listed
+// tasks in LDS (OneHand), dealt heaviest first, and the lists and plans of the first layer in the LDS areas of the rows that run
+// them.  Such a task starts at the state vectors; one of a later layer (more tasks than rows) runs the whole prologue.
+template <int NP, int CPL, int G, int W, int OCC, int LAY, int MODE, int FLAVOR, bool DUMP, bool JUMP, bool BUILD, bool PAIR = false,
+          bool ONE = false>
+__device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand = nullptr)
 {
     constexpr bool HASG = FLAVOR == 0;
     constexpr bool ALLVALID = FLAVOR == 2;
@@ -332,9 +337,10 @@ __device__ __forceinline__ void logl_body(const KParams &p)
     // each while they fit (the other rows of the wave then idle: a row's events -- basis change, comparison, jump --
     // are paid by the whole wave), the next heaviest the second rows, and so on; lists longer than the grid has rows
     // are throughput-bound and tasks of similar work share a wave.
-    const bool listed = JUMP && p.work != nullptr;
-    int64_t n_tasks = p.ntasks;
-    if (listed) {
+    static_assert(!ONE || (LAY == 3 && JUMP && !DUMP && !BUILD), "the one-launch path serves the listed frame loop only");
+    const bool listed = JUMP && (ONE || p.work != nullptr);
+    int64_t n_tasks = ONE ? hand->n : p.ntasks;
+    if (listed && !ONE) {
         int64_t tot = 0;
         for (int bq = 0; bq < kWorkBuckets; ++bq) tot += p.work_counts[bq];
         n_tasks = tot;
@@ -344,11 +350,14 @@ __device__ __forceinline__ void logl_body(const KParams &p)
     // Matrix tables live in LDS for the whole kernel: the dense propagators are needed every frame,
     // and a modal basis change walks its matrix row by row in a dependent loop -- from L2 that was
     // ~500 cycles per row, 10 us per switch (measured: +89 % kernel time at k = 20).
-    for (int i = tid; i < p.tab_doubles; i += kThreads) smem[i] = p.tab[i];
-    // ... and so do the per-state vectors a state switch reloads (lam | wq | sig: the head of each state block)
+    // (ONE: staged by logl_one_kernel, in front of the walk)
     constexpr int HDR = state_header_doubles(NP);
-    for (int i = tid; i < p.S * HDR; i += kThreads) smem[p.tab_doubles + i] = p.states[(size_t)(i / HDR) * StateBlock::size(NP) + i % HDR];
-    __syncthreads();
+    if constexpr (!ONE) {
+        for (int i = tid; i < p.tab_doubles; i += kThreads) smem[i] = p.tab[i];
+        // ... and so do the per-state vectors a state switch reloads (lam | wq | sig: the head of each state block)
+        for (int i = tid; i < p.S * HDR; i += kThreads) smem[p.tab_doubles + i] = p.states[(size_t)(i / HDR) * StateBlock::size(NP) + i % HDR];
+        __syncthreads();
+    }
     // per-group scratch: image of X*A, NP + kDMax columns of NP doubles; its first NP doubles
     // double as the all-gather buffer of the update
     if (grp >= GPW) return; // lanes beyond the last whole group (64 % G != 0) idle
@@ -384,10 +393,16 @@ __device__ __forceinline__ void logl_body(const KParams &p)
     // (listed, and the list fits the rows of the grid: spread -- row j of wave w takes slot j * n_waves + w, every second
     // layer in reverse: the waves that carry the heaviest tasks of one layer get the lightest of the next, or none)
     const bool spread = listed && (BILD_SPREAD_ALWAYS || n_tasks <= gstride);
+    // (ONE: position q of the workgroup's deal runs on wave (q + rot) % W, row (pair) q / W of its layer -- the heaviest task of each
+    // layer on wave `rot`; rot = residency index, so that the two workgroups of a CU do not put their heaviest tasks on one SIMD)
+    const int one_wave = ONE ? (wv + kWaves - (int)(blockIdx.x / 256) % kWaves) % kWaves : 0;
 
-    for (int64_t it = spread ? (int64_t)tgrp : wave_id * TPW + tgrp;; it += spread ? (int64_t)TPW : gstride) {
+    for (int64_t it = ONE ? 0 : spread ? (int64_t)tgrp : wave_id * TPW + tgrp;; it += ONE ? 1 : spread ? (int64_t)TPW : gstride) {
         int64_t task = it;
-        if (spread) { // `it` counts layers of n_waves slots
+        if (ONE) { // `it` counts layers of kWaves * TPW positions
+            task = (it * TPW + tgrp) * kWaves + one_wave;
+            if (task >= n_tasks) break;
+        } else if (spread) { // `it` counts layers of n_waves slots
             if (it * n_waves >= n_tasks) break;
             task = it * n_waves + (BILD_SNAKE && (it & 1) ? n_waves - 1 - wave_id : wave_id);
             if (task >= n_tasks) continue;
@@ -396,7 +411,13 @@ __device__ __forceinline__ void logl_body(const KParams &p)
         }
         int64_t r, otask;
         int e;
-        if (listed) {
+        // (ONE: the first layer's list, plan and expected work are in the row's LDS areas already)
+        const bool handed = ONE && it == 0;
+        if (ONE) {
+            otask = hand->task[task];
+            r = otask / p.dstar_max;
+            e = (int)(otask - r * p.dstar_max);
+        } else if (listed) {
             // slot `task` of the buckets laid end to end, heaviest (last) bucket first
             int64_t q = task;
             int bq = kWorkBuckets - 1;
@@ -423,7 +444,7 @@ __device__ __forceinline__ void logl_body(const KParams &p)
         // for HERE, beside the trajectory descriptor, not behind it; lane i holds entry i, lists of up to kSegLds segments)
         int32_t pre_start = 0, pre_state = 0;
         if constexpr (kLean) {
-            if (K1 <= kSegLds && gl < K1) {
+            if (!handed && K1 <= kSegLds && gl < K1) {
                 pre_start = p.seg_start[r * K1 + gl];
                 pre_state = p.seg_state[r * K1 + gl];
             }
@@ -494,7 +515,9 @@ __device__ __forceinline__ void logl_body(const KParams &p)
         // costs two LDS reads instead of two dependent L2 round trips.  Longer lists are walked in global memory.
         const bool seg_in_lds = K1 <= kSegLds;
         int nseg = K1;
-        if (seg_in_lds) {
+        if (handed) {
+            nseg = __double2loint(walk[1]);
+        } else if (seg_in_lds) {
             volatile int32_t *const sl = seg_lds;
             if constexpr (kLean && (BLK || ROW)) { // (16 lanes per task: one entry per lane, loaded at the top of the task)
                 if (gl < K1) {
@@ -533,7 +556,8 @@ __device__ __forceinline__ void logl_body(const KParams &p)
             int w = 0, run_from = -1, links = 0; // a chain: switches less than m_typ frames apart, run as one piece
             const int mt = p.m_typ;
             const bool pairs = p.trans2 != nullptr;
-            for (int i = 1; i < nseg; ++i) {
+            if (handed) w = __double2hiint(walk[1]); // (the walk's estimate: the same rule on the same list)
+            for (int i = 1; i < (handed ? 0 : nseg); ++i) {
                 const int t1 = seg_lds[i];
                 const int gap = ((i + 1 < nseg) ? seg_lds[i + 1] : T) - t1;
                 if (run_from < 0) {
@@ -550,7 +574,7 @@ __device__ __forceinline__ void logl_body(const KParams &p)
                 }
             }
             // a chain that reaches the end of the trajectory: one switch, or two with the pair table, are table entries too
-            if (run_from >= 0 && !(links == 1 || (pairs && links == 2))) w += T - run_from;
+            if (!handed && run_from >= 0 && !(links == 1 || (pairs && links == 2))) w += T - run_from;
             if (__ballot(w >= BILD_PRIO_T3)) __builtin_amdgcn_s_setprio(3);
             else if (__ballot(w >= BILD_PRIO_T2)) __builtin_amdgcn_s_setprio(2);
             else if (__ballot(w >= BILD_PRIO_T1)) __builtin_amdgcn_s_setprio(1);
@@ -1054,7 +1078,7 @@ __device__ __forceinline__ void logl_body(const KParams &p)
         // once, and leaves the two sums and the two frame counts in LDS; `land` then walks from switch to switch without
         // waiting for memory (four switches: 6.6 -> ~2 us of a task's life; the same numbers, added in the same order).
         const bool planned = use_transients && p.walk_lds != 0 && seg_in_lds;
-        if (planned) {
+        if (planned && !handed) {
             for (int i = 1 + gl; i < nseg; i += (BLK || ROW) ? 16 : G) {
                 const int ti = seg_lds[i], s0 = seg_lds[kSegLds + i - 1], s1 = seg_lds[kSegLds + i];
                 const int n2 = (i + 1 < nseg) ? seg_lds[i + 1] : INT_MAX;
@@ -1487,6 +1511,164 @@ __global__ void __launch_bounds__(64 * W, OCC) logl_kernel(const KParams p)
     logl_body<NP, CPL, G, W, OCC, LAY, MODE, FLAVOR, DUMP, JUMP, BUILD>(p);
 }
 
+// ---- the one-launch path: table walk and listed frame loop in one grid --------------------------------------------------------
+// Where the hand-off stays inside a workgroup (LDS and barriers: no work lists, no atomics, no waiting on other workgroups), the
+// frame loop needs no second launch: each workgroup walks a contiguous slice of the batch and runs the tasks its walk could not
+// finish itself.  A listed task of the first layer finds its cleaned list, its walk plan and its expected frames in the LDS areas
+// of its rows -- written by the walk lane, with the values the frame loop's prologue would compute (the same expressions on the
+// same list, see walk_task.h) -- and starts at the state vectors.  DESIGN.md section 4.
+typedef __attribute__((address_space(3))) char lds_char_t;
+struct OneLayout {
+    int32_t seg0;  // bytes from the LDS base: the rows' segment lists (2 * group_seg_doubles() int32 per row)
+    int32_t walk0; // ... the rows' walk plans (kWalkDoubles per row)
+    int32_t hand0; // ... the OneHand record
+    int32_t gpw;   // rows per wave
+};
+
+// The walk of the workgroup's slice [t0, t1) (<= kOneSlice tasks; slice position j on wave j % W, lane j / W) and the deal of its
+// listed tasks: heaviest first (expected frames, then task index), position q on wave (q + rot) % W, row (pair) q / W.  Inline: the
+// parameters stay kernel arguments (scalar loads; out of line they were a private copy in scratch, read by dependent flat loads), and
+// the staging loads the kernel issued in front of it are waited for together with the walk's first loads, not before them.
+template <int KMAX, bool ST, int W>
+__device__ __forceinline__ void walk_one(const WalkParams &p, int64_t t0, int64_t t1, OneLayout L, lds_char_t *base)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __attribute__((address_space(3))) OneHand *const h = (__attribute__((address_space(3))) OneHand *)(base + L.hand0);
+    const int64_t task = t0 + (int64_t)lane * W + wv;
+    int la[KMAX], lb[KMAX], lm1[KMAX], lm2[KMAX];
+    double lv1[KMAX], lv2[KMAX];
+    unsigned lkeep = 0;
+    double lx0 = 0.0;
+    int lw = 0;
+    int bucket = -1;
+    if (task < t1)
+        bucket = walk_task<KMAX, ST>(p, task, [&](const int (&a)[KMAX], const int (&b)[KMAX], unsigned keep, const double (&v1)[KMAX],
+                                                   const double (&v2)[KMAX], const int (&m1)[KMAX], const int (&m2)[KMAX], double x0, int w) {
+#pragma unroll
+            for (int i = 0; i < KMAX; ++i) {
+                la[i] = a[i];
+                lb[i] = b[i];
+                lv1[i] = v1[i];
+                lv2[i] = v2[i];
+                lm1[i] = m1[i];
+                lm2[i] = m2[i];
+            }
+            lkeep = keep;
+            lx0 = x0;
+            lw = w;
+        });
+    if (p.debug & 2) bucket = -1;
+    const bool listed = bucket >= 0;
+    const unsigned long long mask = __ballot(listed);
+    if (lane == 0) h->cnt[wv] = (int32_t)__popcll(mask);
+    __syncthreads();
+    int n = 0, j = (int)__popcll(mask & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const int c = h->cnt[k];
+        n += c;
+        j += k < wv ? c : 0;
+    }
+    if (listed) {
+        h->reg_task[j] = (int32_t)task;
+        h->reg_w[j] = lw;
+    }
+    if (tid == 0) h->n = n;
+    __syncthreads();
+    if (listed) {
+        int q = 0;
+        for (int k = 0; k < n; ++k) {
+            const int wk = h->reg_w[k], tk = h->reg_task[k];
+            q += (wk > lw || (wk == lw && tk < (int)task)) ? 1 : 0;
+        }
+        h->task[q] = (int32_t)task;
+        const bool pair = n <= W * L.gpw / 2; // (logl_one_kernel: the two-row frame while the tasks fit the row pairs once)
+        const int per_wave = pair ? L.gpw / 2 : L.gpw;
+        if (q < W * per_wave) {
+            const int rot = (int)(blockIdx.x / 256) % W;
+            const int row0 = ((q + rot) % W) * L.gpw + (pair ? 2 * (q / W) : q / W);
+            for (int rr = 0; rr < (pair ? 2 : 1); ++rr) {
+                __attribute__((address_space(3))) int32_t *const sl =
+                    (__attribute__((address_space(3))) int32_t *)(base + L.seg0) + (size_t)(row0 + rr) * (2 * group_seg_doubles());
+                __attribute__((address_space(3))) double *const wk =
+                    (__attribute__((address_space(3))) double *)(base + L.walk0) + (size_t)(row0 + rr) * kWalkDoubles;
+                sl[0] = la[0];
+                sl[kSegLds] = lb[0];
+                wk[0] = lx0;
+                int cnt = 1;
+#pragma unroll
+                for (int i = 1; i < KMAX; ++i) {
+                    if ((lkeep >> i) & 1u) {
+                        sl[cnt] = la[i];
+                        sl[kSegLds + cnt] = lb[i];
+                        wk[3 * cnt] = lv1[i];
+                        wk[3 * cnt + 1] = lv2[i];
+                        wk[3 * cnt + 2] = __hiloint2double(lm2[i], lm1[i]);
+                        ++cnt;
+                    }
+                }
+                wk[1] = __hiloint2double(lw, cnt); // (slots 1 and 2 belong to no switch)
+            }
+        }
+    }
+    __syncthreads();
+}
+
+template <int NP, int CPL, int G, int W, int OCC, int LAY, int FLAVOR>
+__global__ void __launch_bounds__(64 * W, OCC) logl_one_kernel(const KParams p, const WalkParams wp)
+{
+    static_assert(LAY == 3 && CPL == 1 && G == 16 && W <= 4, "the one-launch path serves the listed frame loop (geometry 23)");
+    extern __shared__ __align__(16) double smem[];
+    constexpr int kThreads = 64 * W, GPW = 64 / G, HDR = state_header_doubles(NP);
+    const int64_t ntasks = wp.n * wp.dstar_max;
+    const int64_t slice = (ntasks + gridDim.x - 1) / gridDim.x;
+    const int64_t t0 = (int64_t)blockIdx.x * slice;
+    if (t0 >= ntasks) return;
+    const int64_t t1 = t0 + slice < ntasks ? t0 + slice : ntasks;
+    // the tables of the frame loop, as logl_body stages them: the first kPre doubles per thread are asked for HERE, in front of the
+    // walk, and written to LDS behind it -- their round trip overlaps the walk's first one (the headline model: 460 doubles, all of them)
+    const int tid = threadIdx.x;
+    const int lds_tab = p.tab_doubles + p.S * HDR;
+    auto stage_src = [&](int i) {
+        return i < p.tab_doubles ? p.tab + i : p.states + (size_t)((i - p.tab_doubles) / HDR) * StateBlock::size(NP) + (i - p.tab_doubles) % HDR;
+    };
+    constexpr int kPre = 4;
+    double pre[kPre];
+#pragma unroll
+    for (int u = 0; u < kPre; ++u) {
+        const int i = tid + u * kThreads;
+        pre[u] = i < lds_tab ? *stage_src(i) : 0.0;
+    }
+    OneLayout L;
+    L.seg0 = (lds_tab + W * GPW * group_image_doubles(NP)) * (int)sizeof(double);
+    L.walk0 = (lds_tab + W * GPW * (group_image_doubles(NP) + group_seg_doubles())) * (int)sizeof(double);
+    L.hand0 = L.walk0 + W * GPW * kWalkDoubles * (int)sizeof(double);
+    L.gpw = GPW;
+    lds_char_t *const base = (lds_char_t *)smem;
+    static_assert(kOneLaunchMaxK1 == 5, "one walk instantiation per list length the host sends here");
+    switch (wp.K1) {
+#define BILD_ONE_CASE(KMAX)                                                                  \
+    case KMAX:                                                                               \
+        if (wp.ss) walk_one<KMAX, true, W>(wp, t0, t1, L, base);                           \
+        else walk_one<KMAX, false, W>(wp, t0, t1, L, base);                                \
+        break;
+        BILD_ONE_CASE(1) BILD_ONE_CASE(2) BILD_ONE_CASE(3) BILD_ONE_CASE(4) BILD_ONE_CASE(5)
+#undef BILD_ONE_CASE
+    default: return;
+    }
+#pragma unroll
+    for (int u = 0; u < kPre; ++u)
+        if (tid + u * kThreads < lds_tab) smem[tid + u * kThreads] = pre[u];
+    for (int i = tid + kPre * kThreads; i < lds_tab; i += kThreads) smem[i] = *stage_src(i);
+    __syncthreads();
+    const OneHand *const hand = reinterpret_cast<const OneHand *>(reinterpret_cast<const char *>(smem) + L.hand0);
+    const int n = hand->n;
+    if (n == 0) return; // (every task of the slice finished by the walk)
+    // the two-row frame while the workgroup's tasks fit its row pairs once (logl_kernel makes the same choice for the whole grid)
+    if (n <= W * GPW / 2) logl_body<NP, CPL, G, W, OCC, LAY, kModal, FLAVOR, false, true, false, true, true>(p, hand);
+    else logl_body<NP, CPL, G, W, OCC, LAY, kModal, FLAVOR, false, true, false, false, true>(p, hand);
+}
+
 // The running log-likelihood of every record of the prefix table (common.h), from the sums its builder left in the record: one thread
 // per (task, frame); the sums of the dimensions are added in the order piece_value adds them (lane order: dimension 0, 1, 2).
 __global__ void prefix_L_kernel(const TrajDesc *__restrict__ trajs, int n_traj, int S, int NP, int dstar_max, int blocks_per_task,
@@ -1803,6 +1985,26 @@ int launch_prefix_L(const TrajDesc *d_trajs, int n_traj, int S, int NP, int dsta
     hipLaunchKernelGGL(prefix_L_kernel, dim3((unsigned)(tasks * bpt)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), d_trajs, n_traj, S, NP,
                        dstar_max, bpt, d_prefix, d_prefix_L);
     return (int)hipGetLastError();
+}
+
+int launch_logl_one(const Geometry &g, const KParams &p, const WalkParams &w, int grid, size_t lds, void *stream, void *ev_start, void *ev_stop)
+{
+    if (g.id != 23 || w.K1 < 1 || w.K1 > kOneLaunchMaxK1 || !p.walk_lds || !p.prefix || p.no_jump || !p.trans || p.work) return (int)hipErrorInvalidValue;
+    const int64_t ntasks = w.n * w.dstar_max;
+    if (grid < 1 || (ntasks + grid - 1) / grid > kOneSlice) return (int)hipErrorInvalidValue;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(ev_start), ev1 = reinterpret_cast<hipEvent_t>(ev_stop);
+    auto go = [&](auto k) -> int {
+        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (err != hipSuccess) return (int)err;
+        if (ev0 && ev1) hipExtLaunchKernelGGL(k, dim3(grid), dim3(256), (unsigned)lds, st, ev0, ev1, 0, p, w);
+        else hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, p, w);
+        return (int)hipGetLastError();
+    };
+    const int flavor = p.has_G ? 0 : (p.all_valid ? 2 : 1);
+    if (flavor == 0) return go(logl_one_kernel<10, 1, 16, 4, 2, 3, 0>);
+    if (flavor == 1) return go(logl_one_kernel<10, 1, 16, 4, 2, 3, 1>);
+    return go(logl_one_kernel<10, 1, 16, 4, 2, 3, 2>);
 }
 
 int launch_reduce_partials(const double *partial, double *out, int64_t n, int dstar_max, void *stream)

@@ -193,6 +193,14 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
     // lists of <= 3 segments hold at most two switches: on a set whose tables cover every such candidate the walk finishes
     // the whole batch, and the frame loop -- which would find its lists empty -- is not launched
     const bool frame_loop = !(split && K1 <= 3 && ts.two_switch_covered && p.trans2 != nullptr && !config().no_fused_launch);
+    // ... and where the listed frame loop runs on geometry 23 and the batch is small, walk and frame loop share ONE launch
+    // (kernels.hip: logl_one_kernel): each workgroup walks a slice of at most kOneSlice tasks and runs what it listed itself,
+    // handed over in LDS -- no work lists, no second dispatch, no prologue that repeats the walk.  Bit-identical to the two
+    // kernels (BILD_NO_ONE_LAUNCH) and to BILD_NO_SPLIT.  The bound: DESIGN.md section 4 (profiles/r05_one_launch_ab.txt).
+    const int64_t one_grid = std::min<int64_t>(ntasks, 256 * (int64_t)std::max(geom.OCC, 1));
+    const bool one = split && frame_loop && fam == kVector && geom.id == 23 && geom.lay == 3 && K1 <= kOneLaunchMaxK1 && ntasks >= 1 &&
+                     ntasks <= kOneLaunchMaxTasks && (ntasks + one_grid - 1) / one_grid <= kOneSlice && !config().no_one_launch &&
+                     lds + sizeof(OneHand) <= (size_t)160 * 1024 / (size_t)std::max(1, (4 * geom.OCC + geom.W - 1) / geom.W);
 
     // What this call allocates and creates for itself, released by whatever path it returns: the frees are stream-ordered
     // behind everything the call enqueued, the events are destroyed unless they were handed to the timing lists.
@@ -212,7 +220,7 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
     if (timing) {
         HIP_TRY(hipEventCreate(&own.e0));
         HIP_TRY(hipEventCreate(&own.e1));
-        if (walk) {
+        if (walk && !one) { // (the one launch carries the frame loop's events only: the walk has no dispatch of its own)
             HIP_TRY(hipEventCreate(&own.w0));
             HIP_TRY(hipEventCreate(&own.w1));
         }
@@ -247,8 +255,8 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
         p.seg_start = d_seg_start;
         p.seg_state = d_seg_state;
     }
+    WalkParams w{};
     if (walk) {
-        WalkParams w{};
         w.trajs = ts.d_descs;
         w.S = m.S;
         w.dstar_max = ts.dstar_max;
@@ -267,8 +275,21 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
         }
         w.convert_all = split ? 0 : 1;
         w.no_lists = frame_loop ? 0 : 1;
+        if (one) {
+            // (no work lists: the counter sets of the persistent block stay as they are -- the walk of the next split launch zeroes
+            // the set after the one it takes, and a flip here would hand that launch a set nobody zeroed)
+            w.Lc = ts.d_prefix_L;
+            w.trans = p.trans;
+            w.trans2 = p.trans2;
+            w.gap_max = p.gap_max;
+            w.m_typ = p.m_typ;
+            w.out = target;
+            w.frames_task = p.frames_task;
+            if (config().walk_debug) w.debug = config().walk_debug;
+            p.order = nullptr;
+        }
         bild_model::WorkSlot *flipped = nullptr; // the persistent work-list block this launch alternates the counter set of
-        if (split) {
+        if (split && !one) {
             int32_t *d_work = nullptr, *d_lists = nullptr;
             const size_t list_bytes = (size_t)kWorkBuckets * (size_t)p.ntasks * sizeof(int32_t);
             {
@@ -316,7 +337,7 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
             p.work_cap = w.work_cap;
             p.order = nullptr; // the work lists ARE the launch order
         }
-        const int wrc = launch_walk(w, (void *)st, (void *)own.w0, (void *)own.w1); // (timed: the events ride on the dispatch)
+        const int wrc = one ? 0 : launch_walk(w, (void *)st, (void *)own.w0, (void *)own.w1); // (timed: the events ride on the dispatch)
         if (wrc != 0) {
             if (flipped) { // the walk never ran: the other counter set was not zeroed -- the next launch must not take it
                 std::lock_guard<std::mutex> lk(m.mu);
@@ -324,7 +345,7 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
             }
             return fail(BILD_ERR_HIP, "walk kernel launch failed: %s", hipGetErrorString((hipError_t)wrc));
         }
-        if (timing) {
+        if (timing && !one) {
             std::lock_guard<std::mutex> lk(g_time_mu);
             g_walk_events.emplace_back(own.w0, own.w1);
             own.w0 = own.w1 = nullptr;
@@ -336,12 +357,14 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
     int64_t blocks = (p.ntasks + tasks_per_block - 1) / tasks_per_block;
     // (work lists: one residency of the chip at most -- most of the tasks never reach the frame loop)
     const int64_t max_blocks = split ? 256 * std::max(geom.OCC, 1) : 256 * 16;
-    const int grid = (int)std::min<int64_t>(std::max<int64_t>(blocks, 1), max_blocks);
+    const int grid = one ? (int)one_grid : (int)std::min<int64_t>(std::max<int64_t>(blocks, 1), max_blocks);
     // timed launches of the vector kernels carry their events on the dispatch (start / end of the kernel itself); the tile
     // kernels are bracketed by recorded events (milliseconds long: the brackets' own latency does not matter there)
     const bool ride = fam == kVector;
     if (timing && !ride) HIP_TRY(hipEventRecord(own.e0, st));
     int lrc = !frame_loop          ? 0
+              : one                ? launch_logl_one(geom, p, w, grid, lds + sizeof(OneHand), (void *)st, timing ? (void *)own.e0 : nullptr,
+                                                     timing ? (void *)own.e1 : nullptr)
               : fam == kWide       ? launch_logl_wide(m.NP, p, grid, (void *)st)
               : fam == kModalTiles ? launch_logl_modal_mfma(m.NPm[kModal], p, (void *)st)
               : fam == kDenseTiles ? launch_logl_dense_mfma(m.NPm[kDense], p, (void *)st)
@@ -354,7 +377,7 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
         std::lock_guard<std::mutex> lk(g_time_mu);
         g_time_events.emplace_back(own.e0, own.e1);
         own.e0 = own.e1 = nullptr;
-        g_time_name = fam == kWide ? "logl_wide_kernel" : fam == kModalTiles ? "logl_modal_mfma_kernel" : fam == kDenseTiles ? "logl_dense_mfma_kernel" : kernel_name(geom, mode);
+        g_time_name = fam == kWide ? "logl_wide_kernel" : fam == kModalTiles ? "logl_modal_mfma_kernel" : fam == kDenseTiles ? "logl_dense_mfma_kernel" : one ? "logl_one_kernel<modal>" : kernel_name(geom, mode);
     }
     if (ts.dstar_max > 1) {
         lrc = launch_reduce_partials(target, d_out, n, ts.dstar_max, (void *)st);
