@@ -162,6 +162,8 @@ _SIGNATURES = {
     'bild_exact_evidence': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_int64, ctypes.c_int, ctypes.c_uint,
                                            _vp]),
     'bild_gauss_exact_evidence': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_int64, ctypes.c_int, _vp]),
+    # exact evidence of every k by the segment recursion (gauss_segdp.cpp)
+    'bild_gauss_segment_evidence': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_uint, ctypes.c_int64, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1248,4 +1250,31 @@ def exact_evidence(model, ts, k, transitions, marginals=True, max_profiles=2 ** 
     else:
         check(lib().bild_exact_evidence(model._h, ts._h, int(k), aptr(tr), float(max_profiles), int(scratch_bytes), T_max,
                                         _flags(path), ctypes.byref(spec)))
+    return res
+
+
+class SegdpOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'kl', 'map_logl', 'n_profiles', 'n_omitted', 'map_seg_start',
+                                                      'map_seg_state', 'log_post')]
+
+
+SEGDP_NAN_PROPAGATE, SEGDP_NAN_OMIT = 0, 1
+
+
+def gauss_segment_evidence(model, ts, k_max, transitions, marginals=True, omit=False, scratch_bytes=0):
+    """
+    exact evidence of every k <= k_max of every trajectory of the set (bild_gauss_segment_evidence): a dict of logev, kl,
+    map_logl, n_profiles, n_omitted (n_traj, K), map_seg_start, map_seg_state (n_traj, K, K) int32 and log_post
+    (n_traj, K, S, T_max) or None; K = k_max + 1, T_max the set's longest trajectory
+    """
+    tr = _transitions_u8(transitions, model.S)
+    n, K = ts.n_traj, int(k_max) + 1
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty((n, K)), 'kl': np.empty((n, K)), 'map_logl': np.empty((n, K)),
+           'n_profiles': np.empty((n, K)), 'n_omitted': np.empty((n, K)),
+           'map_seg_start': np.empty((n, K, K), dtype=np.int32), 'map_seg_state': np.empty((n, K, K), dtype=np.int32),
+           'log_post': np.empty((n, K, model.S, T_max)) if marginals else None}
+    spec = SegdpOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
+    check(lib().bild_gauss_segment_evidence(model._h, ts._h, int(k_max), aptr(tr), T_max, SEGDP_NAN_OMIT if omit else SEGDP_NAN_PROPAGATE,
+                                            int(scratch_bytes), ctypes.byref(spec)))
     return res

@@ -81,3 +81,14 @@ int launch_exact_reduce(const ExactReduce &, void *) { return 1; }
 int launch_exact_fold(const ExactFold &, void *) { return 1; }
 size_t exact_reduce_lds(int, int, int, bool) { return 0; }
 } // namespace bild
+#include "gauss_segdp.h"
+namespace bild {
+int launch_segdp_init(const SegdpParams &, bool, void *) { return 1; }
+int launch_segdp_mix(const SegdpParams &, int, void *) { return 1; }
+int launch_segdp_level(const SegdpParams &, int, void *) { return 1; }
+int launch_segdp_blevel(const SegdpParams &, int, void *) { return 1; }
+int launch_segdp_bmix(const SegdpParams &, int, void *) { return 1; }
+int launch_segdp_backtrack(const SegdpParams &, void *) { return 1; }
+int launch_segdp_cover(const SegdpParams &, void *) { return 1; }
+int launch_segdp_carry(const SegdpParams &, void *) { return 1; }
+} // namespace bild

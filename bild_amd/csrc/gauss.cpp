@@ -254,6 +254,17 @@ int bild::internal_gauss_set_lengths(const bild_gauss_model *m, const bild_gauss
     return BILD_OK;
 }
 
+int bild::internal_gauss_set_device(const bild_gauss_model *m, const bild_gauss_trajset *ts, const GaussTraj **d_trajs, void **stream,
+                                    std::mutex **mu)
+{
+    if (!m || !ts) return fail(BILD_ERR_INVALID, "NULL handle");
+    if (ts->model != m) return fail(BILD_ERR_INVALID, "trajectory set belongs to a different model");
+    *d_trajs = ts->d_trajs;
+    *stream = (void *)ts->stream;
+    *mu = const_cast<std::mutex *>(&ts->mu);
+    return BILD_OK;
+}
+
 int bild::internal_gauss_walk_resident(const bild_gauss_model *m, const bild_gauss_trajset *ts, int64_t n, int K1, const int32_t *d_seg_start,
                                        const int32_t *d_seg_state, const int32_t *d_traj_id, double *d_out, void *stream)
 {

@@ -7,8 +7,16 @@ with every valid trace of k + 1 states, in the order `FixedkSampler.fix_exhausti
 (`CFC.full_sample` order), combinations inner (`itertools.combinations` order).  Under the uniform prior over them this
 gives what `fix_exhaustive`, `MAP_profile` and `log_marginal_posterior` give, without the host's `max_fcomplete` cap: at
 T = 1000 and two states there are ~2e3 profiles at k = 1, ~1e6 at k = 2 and ~3.3e8 at k = 3.
+
+`exact_sample` (bild_gauss_segment_evidence) does not enumerate: GenericGaussianModel's log-likelihood
+is a sum of per-segment table entries, so the sums over all profiles of k switches follow from a recursion over segments,
+for every k up to k_max in one call.
 """
+import math
+import warnings
+
 import numpy as np
+from scipy.special import logsumexp
 
 from . import _lib
 from .profiles import Loopingprofile, states_from_segments
@@ -109,3 +117,157 @@ def exact_evidence(trajs, model, k, marginals=True, max_profiles=2 ** 32, scratc
                                log_marginal_posterior=post))
     return out[0] if single else out
 
+
+
+# ---------------------------------------------------------------- every k at once: the segment recursion (section 18)
+
+MAX_K_SEGMENT = 64
+
+
+def segment_profile_count(T, k, transitions):
+    """ profiles of k switches on T frames as an exact integer: C(T - 1, k) x `CFC.N_total(k)` """
+    from .amis import CFC
+    return math.comb(T - 1, k) * int(CFC(transitions).N_total(k)) if 0 <= k <= T - 1 else 0
+
+
+class ExactSamplingResults:
+    """
+    The exact counterpart of `SamplingResults` for one trajectory of a `GenericGaussianModel`: evidence, KL, MAP profile and
+    state marginals of every k = 0 ... k_max under the uniform prior over the profiles of k switches.
+
+    traj, model, dE : as given to `exact_sample`
+    k : 0 ... k_max
+    evidence : log-evidence per k (-inf: no profile of k switches; NaN under nan='propagate' where a profile of k switches
+        uses a NaN window); evidence_se : zeros, the evidence is exact
+    KL : Kullback-Leibler divergence of the posterior from the prior per k
+    n_profiles : profiles the evidence averages over, a list of Python integers (exact; the device's count of the profiles
+        left under nan='omit' is exact below 2^53); n_omitted : profiles left out (nan='omit' only)
+    map_logL : the largest log-likelihood per k (NaN without a profile)
+    """
+
+    def __init__(self, traj, model, dE, evidence, KL, map_logL, n_profiles, n_omitted, map_seg_start, map_seg_state, log_post):
+        self.traj = traj
+        self.model = model
+        self.dE = dE
+        self.evidence = np.asarray(evidence, dtype=np.float64)
+        self.k = np.arange(len(self.evidence))
+        self.evidence_se = np.zeros(len(self.evidence))
+        self.KL = np.asarray(KL, dtype=np.float64)
+        self.map_logL = np.asarray(map_logL, dtype=np.float64)
+        self.n_profiles = list(n_profiles)
+        self.n_omitted = list(n_omitted)
+        self._seg_start = np.asarray(map_seg_start, dtype=np.int32)
+        self._seg_state = np.asarray(map_seg_state, dtype=np.int32)
+        self._log_post = log_post
+
+    def __repr__(self):
+        return f"ExactSamplingResults(T={len(self.traj)}, k_max={len(self.k) - 1}, evidence={self.evidence!r})"
+
+    def map_profile(self, k):
+        """ a profile of k switches of largest log-likelihood as a `Loopingprofile` (None without one) """
+        if self._seg_start[k, 0] < 0:
+            return None
+        return Loopingprofile(states_from_segments(self._seg_start[k:k + 1, :k + 1], self._seg_state[k:k + 1, :k + 1],
+                                                   len(self.traj))[0])
+
+    def best_k(self, dE=None):
+        """ smallest k whose evidence is within dE of the maximum, as `SamplingResults.best_k`; NaN evidences are ignored """
+        if dE is None:
+            dE = self.dE
+        ev = self.evidence
+        bad = np.isnan(ev)
+        if np.all(bad):
+            raise ValueError("every evidence is NaN (profiles with a NaN window at every k): use nan='omit'")
+        if np.any(bad):
+            warnings.warn(f"evidence is NaN for k = {self.k[bad].tolist()}; these k are ignored (nan='omit' leaves the NaN "
+                          f"profiles out instead)", RuntimeWarning, stacklevel=2)
+        ev = np.where(bad, -np.inf, ev)
+        return int(np.min(self.k[ev >= np.max(ev) - dE]))
+
+    def best_profile(self, dE=None):
+        """ MAP profile at `best_k` """
+        return self.map_profile(self.best_k(dE))
+
+    def log_marginal_posterior_k(self, k):
+        """ (S, T) log posterior state marginals of the profiles of k switches """
+        if self._log_post is None:
+            raise ValueError("the marginals were not computed: call exact_sample with marginals=True")
+        return self._log_post[k]
+
+    def log_marginal_posterior(self, dE=None):
+        """
+        (S, T) log posterior state marginals at `best_k`; ``dE='average'`` averages over k weighted by evidence, with
+        `SamplingResults.log_marginal_posterior`'s formula (k with NaN evidence are left out with `best_k`'s warning)
+        """
+        if isinstance(dE, str) and dE == 'average':
+            if self._log_post is None:
+                raise ValueError("the marginals were not computed: call exact_sample with marginals=True")
+            if np.any(np.isnan(self.evidence)):
+                self.best_k(0)      # the warning, or the error when nothing is left
+            with np.errstate(under='ignore'):
+                logpost = logsumexp([self._log_post[k] + logev for k, logev in zip(self.k, self.evidence) if logev > -np.inf],
+                                    axis=0)
+                return logpost - logsumexp(logpost, axis=0)
+        return self.log_marginal_posterior_k(self.best_k(dE))
+
+
+def _check_exact_sample(trajs, model, k_max, nan):
+    """ every refusal of `exact_sample`; returns (single, items, transitions) """
+    from .gauss import GenericGaussianModel
+    if not isinstance(model, GenericGaussianModel):
+        raise TypeError(f"exact_sample needs a GenericGaussianModel, whose log-likelihood is a sum of segment terms, not "
+                        f"{type(model).__name__}")
+    if isinstance(k_max, bool) or not isinstance(k_max, (int, np.integer)) or not 0 <= k_max <= MAX_K_SEGMENT:
+        raise ValueError(f"k_max = {k_max!r}: the segment recursion supports integers 0 <= k_max <= {MAX_K_SEGMENT}")
+    if nan not in ('propagate', 'omit'):
+        raise ValueError(f"nan = {nan!r}: 'propagate' or 'omit'")
+    S = model.msd.shape[0]      # (nStates is read off transitions)
+    transitions = np.asarray(model.transitions, dtype=bool)
+    if transitions.shape != (S, S):
+        raise ValueError(f"model.transitions has shape {transitions.shape}; ({S}, {S}) expected")
+    single = not isinstance(trajs, (list, tuple))
+    items = [trajs] if single else list(trajs)
+    for t in items:
+        if len(t) > model.max_T:
+            raise ValueError(f"trajectory of {len(t)} frames: GenericGaussianModel evaluates at most {model.max_T} frames")
+    return single, items, transitions
+
+
+def results_from_arrays(traj, model, dE, transitions, res, j=0):
+    """ `ExactSamplingResults` of trajectory j from arrays shaped as `_lib.gauss_segment_evidence` returns them """
+    T = len(traj)
+    K = res['logev'].shape[1]
+    n_omitted = [int(x) for x in res['n_omitted'][j]]
+    n_profiles = [segment_profile_count(T, k, transitions) - n_omitted[k] for k in range(K)]
+    post = None if res['log_post'] is None else res['log_post'][j, :, :, :T].copy()
+    return ExactSamplingResults(traj, model, dE, res['logev'][j].copy(), res['kl'][j].copy(), res['map_logl'][j].copy(), n_profiles,
+                                n_omitted, res['map_seg_start'][j].copy(), res['map_seg_state'][j].copy(), post)
+
+
+def exact_sample(trajs, model, dE=0, k_max=20, marginals=True, nan='propagate', scratch_bytes=0):
+    """
+    Everything `sample` produces for a `GenericGaussianModel` -- evidence per k, best k, MAP profile, state marginals --
+    exactly and for every k = 0 ... k_max at once, by a recursion over segments on the GPU (no sampler, no `evidence_se`,
+    no `max_fcomplete`).
+
+    trajs : a trajectory or a list of them; a list gives a list of results from ONE device call
+    model : a `GenericGaussianModel` (anything else: TypeError -- the log-likelihood must be a sum of segment terms)
+    dE : the default of `best_k` and the methods built on it
+    k_max : largest number of switches, 0 <= k_max <= 64; k beyond T - 1 carry evidence -inf
+    marginals : compute the state marginals of every k
+    nan : 'propagate' -- a k with a profile that uses a NaN window (a later ss_order-0 segment without a valid frame) has NaN
+        evidence, KL and marginals; 'omit' -- such profiles are left out of the sums and of the count (`n_omitted`)
+    scratch_bytes : device workspace of one chunk of whole trajectories (0: at most 1 GiB and a third of the free memory)
+
+    MAP ties (every switch frame inside a gap gives the same log-likelihood) are broken on the trajectory's own tables: the
+    smallest final state, then from the last switch backwards the smallest switch frame and the smallest preceding state.
+    Every refusal is raised before the trajectories are uploaded.  Returns `ExactSamplingResults` or a list of them.
+    """
+    single, items, transitions = _check_exact_sample(trajs, model, k_max, nan)
+    if not items:
+        return []
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_segment_evidence(model.handle(), ts, int(k_max), transitions, marginals=marginals, omit=nan == 'omit',
+                                      scratch_bytes=scratch_bytes)
+    out = [results_from_arrays(t, model, dE, transitions, res, j) for j, t in enumerate(items)]
+    return out[0] if single else out

@@ -844,6 +844,43 @@ int bild_exact_evidence(const bild_model *m, const bild_trajset *ts, int k, cons
 int bild_gauss_exact_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k, const uint8_t *transitions,
                               double max_profiles, int64_t scratch_bytes, int T_max, bild_exact_out *out);
 
+/* ---------------------------------------------------------------- exact evidence of every k by a segment recursion ----
+ * GenericGaussianModel only.  The log-likelihood of a profile is a sum of per-segment table
+ * entries, F[n_0][t1_0] + sum_i W[n_i][t0_i - 1][t1_i], so the sums over all profiles of k switches -- the profiles and the
+ * uniform prior of "exact evidence by enumeration" above -- follow from a semi-Markov forward recursion over segments, for
+ * every k = 0 .. k_max in one call and in O(k_max S T^2) terms.  With K = k_max + 1, per trajectory and k:
+ *   logev        log mean exp(logL) over the profiles of k switches (-inf: no profile)
+ *   kl           posterior mean of logL minus logev (NaN without profiles)
+ *   map_logl     the largest logL, and map_seg_start / map_seg_state a profile that attains it: k + 1 segments, the rest
+ *                of the row of K entries padded with empty segments at T in state 0 (-1 everywhere: no profile).
+ *                Among equal maxima the smallest final state wins, then, from the last switch to the first, the
+ *                smallest switch frame and then the smallest preceding state: a rule on the trajectory's own tables.
+ *   n_profiles   profiles the mean is taken over; n_omitted: profiles left out of it (both as doubles, exact below 2^53)
+ *   log_post     (NULL: not computed) normalised log marginal posterior of the state per frame, K x S x T_max per
+ *                trajectory, NaN behind its T; sums of non-negative terms only.
+ * A profile that uses a NaN window ("Deviation") is never a MAP candidate.  flags = 0
+ * (BILD_SEGDP_NAN_PROPAGATE): logev, kl and log_post of a k with such a profile are NaN, n_profiles counts every profile
+ * and n_omitted is 0.  BILD_SEGDP_NAN_OMIT: such profiles are left out of the sums and of n_profiles, and counted in
+ * n_omitted.  A term of weight -inf weighs 0 and adds 0 to kl.  A k without a profile (T - 1 < k, or no valid trace) does
+ * not affect the others.  No floating-point atomics: every reduction has a fixed order that depends on the trajectory
+ * alone, so results are bit-identical across calls, the order of the set, a trajectory alone or in a batch, and
+ * scratch_bytes (chunks of whole trajectories; 0: at most 1 GiB and a third of the free device memory; at least one
+ * trajectory).  Refused before any device work: k_max outside 0 .. 64 (BILD_ERR_UNSUPPORTED), unknown flags, a transitions
+ * entry other than 0 / 1, T_max shorter than a trajectory of the set, a negative scratch_bytes (BILD_ERR_INVALID).
+ * Plain launches on the set's stream.  Synchronous. */
+#define BILD_SEGDP_NAN_PROPAGATE 0u
+#define BILD_SEGDP_NAN_OMIT 1u
+
+typedef struct bild_segdp_out {
+    double *logev, *kl, *map_logl;          /* n_traj x K each */
+    double *n_profiles, *n_omitted;         /* n_traj x K */
+    int32_t *map_seg_start, *map_seg_state; /* n_traj x K x K */
+    double *log_post;                       /* n_traj x K x S x T_max, NULL = marginals not computed */
+} bild_segdp_out;                           /* every pointer may be NULL: not written */
+
+int bild_gauss_segment_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k_max, const uint8_t *transitions,
+                                int T_max, unsigned flags, int64_t scratch_bytes, bild_segdp_out *out);
+
 #ifdef __cplusplus
 }
 #endif
