@@ -273,6 +273,41 @@ __device__ __forceinline__ void matvec_to_lds(XPtr X, const Cols<NP, CPL> &in, d
     }
 }
 
+// The same product for a row of a PAIR: out[k] = sum_m X[2k + odd][m] * in[m], the outputs this row keeps (X points at row `odd` of the
+// matrix).  One matrix row per trip, the row of trip k + 1 asked for in front of the FMAs of trip k (two register sets of NP doubles),
+// every output formed as above -- one accumulator over even m, one over odd m, m ascending, then their sum: the same bits.  STORE: the
+// outputs of the lanes with `store` also go to Tg[2k] (Tg points at entry `odd` of the lane's column in the pair's image).
+template <int NP, bool STORE, typename XPtr>
+__device__ __forceinline__ void matvec_pair(XPtr X, const double (&in)[NP], double (&out)[NP / 2], double *__restrict__ Tg, bool store)
+{
+    static_assert(NP % 2 == 0, "a row of a pair holds every second entry");
+    constexpr int H = NP / 2;
+    double2 cur[H], nxt[H];
+#pragma unroll
+    for (int k2 = 0; k2 < H; ++k2) cur[k2] = *reinterpret_cast<const double2 *>(X + 2 * k2);
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        if (k + 1 < H) {
+#pragma unroll
+            for (int k2 = 0; k2 < H; ++k2) nxt[k2] = *reinterpret_cast<const double2 *>(X + 2 * (k + 1) * NP + 2 * k2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        double a = 0.0, a2 = 0.0;
+#pragma unroll
+        for (int k2 = 0; k2 < H; ++k2) {
+            a = fma(cur[k2].x, in[2 * k2], a);
+            a2 = fma(cur[k2].y, in[2 * k2 + 1], a2);
+        }
+        out[k] = a + a2;
+        if constexpr (STORE) {
+            if (store) Tg[2 * k] = out[k];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k2 = 0; k2 < H; ++k2) cur[k2] = nxt[k2];
+    }
+}
+
 // FLAVOR selects what the frame loop has to carry:
 //   0: external force (G != 0) and missing frames   1: missing frames   2: neither (every frame valid)
 // LAY: 0 packed groups of G consecutive lanes; 1 a group is a 16-lane block of the f64 4x4x4 matrix instruction
@@ -287,8 +322,10 @@ __device__ __forceinline__ void matvec_to_lds(XPtr X, const Cols<NP, CPL> &in, d
 // compiled into both: configs[3] tables 234 -> 406 ms.)
 // PAIR: the two-row frame of the listed loop (LAY 3 only, see logl_kernel): a task runs on a pair of rows, lane j of the even
 // row holds the even entries of column j of [C | M], the odd row the odd ones -- half the predict, dot and rank-1 instructions of
-// a frame.  Everything else (prologue, events, epilogue) runs in both rows alike on whole columns, unpacked from the halves at an
-// event and packed again behind it; both rows then hold the same bits, so they take the same branches.
+// a frame.  The events work on the halves too: a basis change computes in each row the outputs that row keeps (sandwich_pair), a
+// look at the table takes its maxima over the row's entries and exchanges them (compare_with_table) -- whole columns exist only as
+// the input of a basis change, in the tail of a look and where a record is loaded.  Whatever decides a branch is exchanged first, so
+// both rows hold the same bits there and take the same branches.
 // ONE: the listed frame loop of the one-launch path (logl_one_kernel): the workgroup's own table walk (walk_one) has left its listed
 // tasks in LDS (OneHand), dealt heaviest first, and the lists and plans of the first layer in the LDS areas of the rows that run
 // them.  Such a task starts at the state vectors; one of a later layer (more tasks than rows) runs the whole prologue.
@@ -437,7 +474,7 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
         }
 #ifdef BILD_TASK_CLOCK
         const unsigned long long clock_begin = wall_clock64(); // diagnostics build only: tools/task_clock.py
-        unsigned long long clock_events = 0;                   // (== 2: ticks inside comparisons / jumps, and how many)
+        unsigned long long clock_events = 0;                   // (== 2: ticks inside comparisons / jumps, and how many; == 4: inside basis changes)
         int n_events = 0;
 #endif
         // (the listed frame loop: a lone task's prologue is a string of dependent memory round trips -- the task's list is asked
@@ -673,6 +710,8 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
             }
         }
 
+        pack(); // (PAIR: from here on the halves are the state)
+
         double accq[CPL]; // per own column: sum of e^2 / S (meaningful for mean columns)
 #pragma unroll
         for (int q = 0; q < CPL; ++q) accq[q] = 0.0;
@@ -843,6 +882,36 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
             wave_lds_fence();
         };
 
+        // The basis change of a PAIR, split over its rows: both products need whole columns as input (unpacked once, in front),
+        // but each row computes only the outputs it keeps -- entries 2k + odd.  Left product: a mean column's outputs are its new
+        // colh already; the covariance columns' go to ONE image shared by the pair (the even row's area), from which row c is read
+        // back transposed, whole.  Right product: its outputs ARE colh -- no second image, no second read-back, no pack().  Half
+        // the FMAs and half the matrix reads of `sandwich` per lane, and every output sees the operands of the one-row frame in
+        // the same order.  (A spare column is zero and stays zero.)
+        auto sandwich_pair = [&](auto X) {
+            if constexpr (PAIR) {
+                constexpr int H = NP / 2;
+                double *const img = scratch - odd * group_image_doubles(NP);
+                unpack();
+                double left[H], right[H];
+                matvec_pair<NP, true>(X + odd * NP, col.v[0], left, img + cidx[0] * NP + odd, isC[0]);
+                wave_lds_fence();
+                {
+                    const int c = isC[0] ? cidx[0] : 0; // (the other lanes: anything in range, their product is not kept)
+                    double tmp[NP];
+#pragma unroll
+                    for (int i = 0; i < NP; ++i) tmp[i] = img[c + i * NP];
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < NP; ++i) col.v[0][i] = tmp[i];
+                }
+                matvec_pair<NP, false>(X + odd * NP, col.v[0], right, nullptr, false);
+#pragma unroll
+                for (int k = 0; k < H; ++k) colh[k] = isC[0] ? right[k] : (hasImg[0] ? left[k] : 0.0);
+                wave_lds_fence(); // (the image is read: the next writer of the area may come)
+            }
+        };
+
 #ifndef BILD_JUMP_FIRST
 #define BILD_JUMP_FIRST 24
 #endif
@@ -869,12 +938,20 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                         // basis change: one matrix R[sn][s], or -- many states -- out of the old basis (Q[s]) and
                         // into the new one (Q[sn]^T)
                         const int steps = p.tab_factored ? 2 : 1;
+#if defined(BILD_TASK_CLOCK) && BILD_TASK_CLOCK == 4
+                        const unsigned long long ev0 = wall_clock64();
+#endif
                         for (int st = 0; st < steps; ++st) {
                             const int slot = p.tab_factored ? (st == 0 ? s : S + sn) : sn * S + s;
 #ifndef BILD_EXPERIMENT_NO_SANDWICH // timing experiment only (wrong results): what the basis change itself costs
-                            sandwich(const_cast<const double *>(smem) + (size_t)slot * MS, [] {});
+                            if constexpr (PAIR) sandwich_pair(const_cast<const double *>(smem) + (size_t)slot * MS);
+                            else sandwich(const_cast<const double *>(smem) + (size_t)slot * MS, [] {});
 #endif
                         }
+#if defined(BILD_TASK_CLOCK) && BILD_TASK_CLOCK == 4
+                        clock_events += wall_clock64() - ev0;
+                        ++n_events;
+#endif
                     }
                     note_switch(s, t);
                     s = sn;
@@ -982,6 +1059,9 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                     col.v[q][i + 1] = keep * t2.y;
                 }
             }
+            // (PAIR: whole columns in both rows, five 16-byte loads, then the row's half by selects.  Loading the halves directly --
+            // five 8-byte loads per row -- was slower: DESIGN.md section 4)
+            pack();
         };
         // lanes of this task, as a mask over the wavefront (for the row-wide verdict of a comparison)
         unsigned long long group_mask;
@@ -1201,9 +1281,7 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
             nrun = -1; // the run starts at frame 1
             fetch(xc, pc); // frame 0
             fetch(xn, pn); // frame 1 (or the first padding row)
-            pack();
             if (ALLVALID || !isnan(pc)) update(xc);
-            unpack();
         }
         // this launch builds the prefix table: the state after every frame goes to its record (tasks have K1 = 1, s is fixed)
         auto dump = [&](int tt) {
@@ -1276,11 +1354,28 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                 // did not produce (an offset, outliers) the innovations e grow with the data, the log-likelihood error of a
                 // deviation d is ~ 20 |e| d / S, and the floor must not grow with them: TrajDesc::mscale)
                 double dev = 0.0, ref = isM[q] ? td->mscale[e] : 0.0;
+                if constexpr (PAIR) {
+                    // each row over its entries, then the larger of the two: a maximum (fmax: of the operands that are numbers)
+                    // does not depend on the order it is taken in, so both rows hold what the whole column gives
+                    double devh = 0.0, refh = ref;
 #pragma unroll
-                for (int i = 0; i < NP; i += 2) {
-                    const double2 r2 = *reinterpret_cast<const double2 *>(rec + cidx[q] * NP + i);
-                    dev = fmax(dev, fmax(fabs(col.v[q][i] - r2.x), fabs(col.v[q][i + 1] - r2.y)));
-                    ref = fmax(ref, fmax(fabs(r2.x), fabs(r2.y)));
+                    for (int k = 0; k < NP / 2; ++k) {
+                        const double rk = rec[cidx[q] * NP + 2 * k + odd];
+                        devh = fmax(devh, fabs(colh[k] - rk));
+                        refh = fmax(refh, fabs(rk));
+                    }
+                    double d0, d1, r0, r1;
+                    pair_swap(devh, d0, d1);
+                    pair_swap(refh, r0, r1);
+                    dev = fmax(d0, d1);
+                    ref = fmax(r0, r1);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < NP; i += 2) {
+                        const double2 r2 = *reinterpret_cast<const double2 *>(rec + cidx[q] * NP + i);
+                        dev = fmax(dev, fmax(fabs(col.v[q][i] - r2.x), fabs(col.v[q][i + 1] - r2.y)));
+                        ref = fmax(ref, fmax(fabs(r2.x), fabs(r2.y)));
+                    }
                 }
                 const double bar = kJumpTol * ref;
                 same = same && (dev <= bar); // a NaN anywhere never compares equal
@@ -1324,6 +1419,9 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                     }
                     if (far) {
                         converged = true;
+                        // (PAIR: the one place of a look that needs whole columns -- g . (M - M_table) is a chain of NP FMAs
+                        // per lane whose order is part of the result; a chain takes at most one tail)
+                        if constexpr (PAIR) unpack();
                         double mine[CPL];
 #pragma unroll
                         for (int q = 0; q < CPL; ++q) {
@@ -1394,7 +1492,6 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                 return next_start < tc ? next_start : tc;
             };
             int t_event = next_event();
-            pack();
             while (t < T) {
                 // invariant: xn holds frame t, the pointers stand at frame t + 1.  The next frame's data are asked for FIRST, in
                 // front of the branch: in one basic block with the frame the scheduler sinks the load behind the last use of the
@@ -1403,14 +1500,12 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                 for (int q = 0; q < CPL; ++q) xc[q] = xn[q];
                 pc = pn;
                 fetch(xn, pn);
-                if (t >= t_event) {
-                    unpack();
+                if (t >= t_event) { // (PAIR: the events work on the halves, each row on its own)
                     if (jumping && t == t_check) {
                         (void)compare_with_table();
                         if (t >= T) break;
                     }
                     if (t >= next_start) enter_segment(t);
-                    pack();
                     t_event = next_event();
                 }
                 frame(xc, pc);
@@ -1482,7 +1577,7 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                                              (((clock_c - clock_begin) / 2) & 0x3ff));
         else if (false)
 #endif
-            p.frames_task[otask] = BILD_TASK_CLOCK == 2 ? (int32_t)(((clock_events & 0xffffull) << 16) | (unsigned)n_events)
+            p.frames_task[otask] = (BILD_TASK_CLOCK == 2 || BILD_TASK_CLOCK == 4) ? (int32_t)(((clock_events & 0xffffull) << 16) | (unsigned)n_events)
                                                         : (int32_t)(((clock_begin & 0xffffull) << 16) | (wall_clock64() & 0xffffull));
 #else
         if (p.frames_task && lead) p.frames_task[otask] = nrun;

@@ -1,7 +1,10 @@
 """
 The listed frame loop, task by task (diagnostics builds with -DBILD_TASK_CLOCK=1 / =3 in bild_amd/variants/): when every
 listed task of the headline batch begins and ends (100 MHz wall clock), how many frames it ran, and the stamps inside its
-prologue.      python tools/listed_clock.py [n] [T] [k]
+prologue.  With the builds -DBILD_TASK_CLOCK=2 (`events`: ticks inside looks at the table, jumps included) and =4 (`basis`: ticks
+inside basis changes) beside them, the anatomy of the ten tasks that end last.  BILD_CLOCK_TAG=x takes libbild_amd_x{clock,stages,
+events,basis}.so, BILD_CLOCK_NORM the build without clocks (default: the committed one).
+    python tools/listed_clock.py [n] [T] [k]
 """
 import os, sys, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,8 +37,12 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 k = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 res = {}
-for name, lib in (('norm', os.path.join(ROOT, 'bild_amd', 'libbild_amd.so')), ('clock', os.path.join(VDIR, 'libbild_amd_clock.so')),
-                  ('stages', os.path.join(VDIR, 'libbild_amd_stages.so'))):
+tag = os.environ.get('BILD_CLOCK_TAG', '')
+libs = [('norm', os.environ.get('BILD_CLOCK_NORM') or os.path.join(ROOT, 'bild_amd', 'libbild_amd.so'))]
+libs += [(name, os.path.join(VDIR, f'libbild_amd_{tag}{name}.so')) for name in ('clock', 'stages', 'events', 'basis')]
+for name, lib in libs:
+    if not os.path.exists(lib):
+        continue
     path = f'/tmp/listed_clock_{name}.npy'
     r = subprocess.run([sys.executable, __file__, '--child', str(n), str(T), str(k), path], env=dict(os.environ, BILD_AMD_LIB=lib), capture_output=True, text=True)
     if r.returncode != 0:
@@ -48,7 +55,7 @@ b, e = (c >> 16) & 0xffff, c & 0xffff
 t0 = b[listed].min()
 b, e = ((b - t0) & 0xffff) / 100., ((e - t0) & 0xffff) / 100.
 dur = e - b
-v = res['stages'].astype(np.int64) & 0x3fffffff
+v = res.get('stages', np.zeros_like(res['norm'])).astype(np.int64) & 0x3fffffff
 ta, tb, tc = ((v >> 20) & 0x3ff) / 50., ((v >> 10) & 0x3ff) / 50., (v & 0x3ff) / 50.
 print(f"n={n} T={T} k={k}: {listed.sum()} listed tasks, frames run mean {f[listed].mean():.1f} max {f[listed].max()}; tasks begin {b[listed].min():.1f}..{b[listed].max():.1f} us, "
       f"end {e[listed].min():.1f}..{e[listed].max():.1f} us (p50 {np.median(e[listed]):.1f}, p90 {np.percentile(e[listed], 90):.1f})")
@@ -59,3 +66,21 @@ print(f"  task time ~ {coef[0]:.1f} us + {coef[1]:.3f} us x frames")
 order = np.argsort(-e * listed)[:10]
 for i in order:
     print(f"  late task {i:5d}: {f[i]:4d} frames, begins {b[i]:5.1f}, ends {e[i]:5.1f} us ({dur[i]:.1f} us; {(dur[i] - coef[0]) / max(f[i], 1):.3f} us per frame beyond the fit's offset); prologue {tc[i]:.1f} us")
+# the same ten, part by part: ticks inside events from the builds that stamp them (each build's own run: the parts of one row come
+# from different launches of the same batch and add up only as far as the launches repeat)
+if 'events' in res or 'basis' in res:
+    parts = {}
+    for name in ('events', 'basis'):
+        if name in res:
+            v = res[name].astype(np.int64) & 0xffffffff
+            parts[name] = (((v >> 16) & 0xffff) / 100., v & 0xffff)
+    for i in order:
+        txt = ', '.join(f"{name} {parts[name][1][i]} taking {parts[name][0][i]:.2f} us" for name in parts)
+        rest = dur[i] - sum(parts[name][0][i] for name in parts) - tc[i]
+        print(f"  late task {i:5d}: {f[i]:4d} frames, {dur[i]:.1f} us = prologue {tc[i]:.1f} + {txt} + frames and epilogue {rest:.1f} us "
+              f"({rest / max(f[i], 1):.3f} us per frame)")
+    sel = order
+    for name in parts:
+        n_ev = parts[name][1][sel].sum()
+        print(f"  {name}: {parts[name][0][sel].sum() / max(n_ev, 1):.2f} us each over the ten late tasks ({n_ev} of them); "
+              f"all listed tasks: {parts[name][0][listed].sum() / max(parts[name][1][listed].sum(), 1):.2f} us each")
