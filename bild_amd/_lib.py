@@ -164,6 +164,9 @@ _SIGNATURES = {
     'bild_gauss_exact_evidence': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_int64, ctypes.c_int, _vp]),
     # exact evidence of every k by the segment recursion (gauss_segdp.cpp)
     'bild_gauss_segment_evidence': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_uint, ctypes.c_int64, _vp]),
+    # exact posterior draws from the segment recursion's backward tables (gauss_segdraw.cpp)
+    'bild_gauss_segment_draw': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _ip, _ip, _dp,
+                                               ctypes.c_uint64, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1277,4 +1280,31 @@ def gauss_segment_evidence(model, ts, k_max, transitions, marginals=True, omit=F
     spec = SegdpOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
     check(lib().bild_gauss_segment_evidence(model._h, ts._h, int(k_max), aptr(tr), T_max, SEGDP_NAN_OMIT if omit else SEGDP_NAN_PROPAGATE,
                                             int(scratch_bytes), ctypes.byref(spec)))
+    return res
+
+
+class SegdrawOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('seg_start', 'seg_state', 'logl', 'uniforms_out')]
+
+
+def gauss_segment_draw(model, ts, k_max, transitions, draw_traj, draw_k, uniforms=None, seed=0, scratch_bytes=0):
+    """
+    exact posterior draws of profiles (bild_gauss_segment_draw): draw r on trajectory draw_traj[r] of the set with draw_k[r]
+    switches, from its row of ``uniforms`` (n, max(1, 2 k_max)) or, without them, from Philox stream r of ``seed``.  A dict of
+    seg_start, seg_state (n, K) int32, logl (n,) and uniforms (n, max(1, 2 k_max)): those consumed; K = k_max + 1
+    """
+    tr = _transitions_u8(transitions, model.S)
+    draw_traj, draw_k = i32(draw_traj), i32(draw_k)
+    n, K, U = len(draw_traj), int(k_max) + 1, max(1, 2 * int(k_max))
+    assert draw_traj.shape == (n,) and draw_k.shape == (n,)
+    if uniforms is not None:
+        uniforms = f64(uniforms)
+        assert uniforms.shape == (n, U)
+    res = {'seg_start': np.empty((n, K), dtype=np.int32), 'seg_state': np.empty((n, K), dtype=np.int32), 'logl': np.empty(n),
+           'uniforms': np.zeros((n, U))}
+    spec = SegdrawOut(seg_start=aptr(res['seg_start']), seg_state=aptr(res['seg_state']), logl=aptr(res['logl']),
+                      uniforms_out=aptr(res['uniforms']))
+    check(lib().bild_gauss_segment_draw(model._h, ts._h, int(k_max), aptr(tr), int(np.max(ts.T)), int(scratch_bytes), n, iptr(draw_traj),
+                                        iptr(draw_k), None if uniforms is None else aptr(uniforms), int(seed) & (2 ** 64 - 1),
+                                        ctypes.byref(spec)))
     return res

@@ -92,3 +92,8 @@ int launch_segdp_backtrack(const SegdpParams &, void *) { return 1; }
 int launch_segdp_cover(const SegdpParams &, void *) { return 1; }
 int launch_segdp_carry(const SegdpParams &, void *) { return 1; }
 } // namespace bild
+#include "gauss_segdraw.h"
+namespace bild {
+int launch_segdraw_head(const SegdrawParams &, void *) { return 1; }
+int launch_segdraw(const SegdrawParams &, const SegdrawParams *, void *) { return 1; }
+} // namespace bild

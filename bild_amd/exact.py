@@ -11,6 +11,9 @@ T = 1000 and two states there are ~2e3 profiles at k = 1, ~1e6 at k = 2 and ~3.3
 `exact_sample` (bild_gauss_segment_evidence) does not enumerate: GenericGaussianModel's log-likelihood
 is a sum of per-segment table entries, so the sums over all profiles of k switches follow from a recursion over segments,
 for every k up to k_max in one call.
+
+`exact_draw` (bild_gauss_segment_draw) draws profiles from that exact posterior, segment by segment
+against the recursion's backward tables: independent draws, without weights or burn-in.
 """
 import math
 import warnings
@@ -143,12 +146,15 @@ class ExactSamplingResults:
     n_profiles : profiles the evidence averages over, a list of Python integers (exact; the device's count of the profiles
         left under nan='omit' is exact below 2^53); n_omitted : profiles left out (nan='omit' only)
     map_logL : the largest log-likelihood per k (NaN without a profile)
+    nan : the NaN mode the results were made with ('propagate' or 'omit')
     """
 
-    def __init__(self, traj, model, dE, evidence, KL, map_logL, n_profiles, n_omitted, map_seg_start, map_seg_state, log_post):
+    def __init__(self, traj, model, dE, evidence, KL, map_logL, n_profiles, n_omitted, map_seg_start, map_seg_state, log_post,
+                 nan='propagate'):
         self.traj = traj
         self.model = model
         self.dE = dE
+        self.nan = nan
         self.evidence = np.asarray(evidence, dtype=np.float64)
         self.k = np.arange(len(self.evidence))
         self.evidence_se = np.zeros(len(self.evidence))
@@ -210,6 +216,23 @@ class ExactSamplingResults:
                 return logpost - logsumexp(logpost, axis=0)
         return self.log_marginal_posterior_k(self.best_k(dE))
 
+    def draw(self, n, k=None, dE=None, seed=0, uniforms=None):
+        """ n profiles drawn from the exact posterior as `ExactDraws`: `exact_draw` of these results """
+        return exact_draw(self, n, k=k, dE=dE, seed=seed, uniforms=uniforms)
+
+    def posterior_distance(self, n=1000, dE=None, seed=0):
+        """
+        (mean, var), each (T, d): the smoothed track averaged over n profiles drawn from the exact posterior at `best_k(dE)`,
+        or with ``dE='average'`` over k by evidence, in one `model.kalman_mixture` call with equal weights -- the counterpart
+        of `SamplingResults.posterior_distance`, whose weighted samples the exact draws replace.
+        """
+        if isinstance(dE, str) and dE == 'average':
+            draws = exact_draw(self, n, k='average', seed=seed)
+        else:
+            draws = exact_draw(self, n, k=None, dE=dE, seed=seed)
+        mean, var = self.model.kalman_mixture((draws.seg_start, draws.seg_state), [self.traj], np.zeros(len(draws.k)))
+        return mean[0], var[0]
+
 
 def _check_exact_sample(trajs, model, k_max, nan):
     """ every refusal of `exact_sample`; returns (single, items, transitions) """
@@ -233,7 +256,7 @@ def _check_exact_sample(trajs, model, k_max, nan):
     return single, items, transitions
 
 
-def results_from_arrays(traj, model, dE, transitions, res, j=0):
+def results_from_arrays(traj, model, dE, transitions, res, j=0, nan='propagate'):
     """ `ExactSamplingResults` of trajectory j from arrays shaped as `_lib.gauss_segment_evidence` returns them """
     T = len(traj)
     K = res['logev'].shape[1]
@@ -241,7 +264,7 @@ def results_from_arrays(traj, model, dE, transitions, res, j=0):
     n_profiles = [segment_profile_count(T, k, transitions) - n_omitted[k] for k in range(K)]
     post = None if res['log_post'] is None else res['log_post'][j, :, :, :T].copy()
     return ExactSamplingResults(traj, model, dE, res['logev'][j].copy(), res['kl'][j].copy(), res['map_logl'][j].copy(), n_profiles,
-                                n_omitted, res['map_seg_start'][j].copy(), res['map_seg_state'][j].copy(), post)
+                                n_omitted, res['map_seg_start'][j].copy(), res['map_seg_state'][j].copy(), post, nan=nan)
 
 
 def exact_sample(trajs, model, dE=0, k_max=20, marginals=True, nan='propagate', scratch_bytes=0):
@@ -269,5 +292,152 @@ def exact_sample(trajs, model, dE=0, k_max=20, marginals=True, nan='propagate', 
     ts = model.trajset(items[0] if single else items)
     res = _lib.gauss_segment_evidence(model.handle(), ts, int(k_max), transitions, marginals=marginals, omit=nan == 'omit',
                                       scratch_bytes=scratch_bytes)
-    out = [results_from_arrays(t, model, dE, transitions, res, j) for j, t in enumerate(items)]
+    out = [results_from_arrays(t, model, dE, transitions, res, j, nan=nan) for j, t in enumerate(items)]
+    return out[0] if single else out
+
+
+# ---------------------------------------------------------------- profiles drawn from the exact posterior (section 19)
+
+class ExactDraws:
+    """
+    Profiles of one trajectory drawn independently from the exact posterior (`exact_draw`).
+
+    k : (n,) switches of each draw; `n_switches` is the same array
+    seg_start, seg_state : (n, k_max + 1) int32 run-length rows, k + 1 segments each, padded with empty segments at T in
+        state 0 (the layout of `model.logL_segments` and `model.kalman_mixture`)
+    logL : (n,) log-likelihood of each drawn profile, from the same tables
+    uniforms : (n, max(1, 2 k_max)) the uniforms each draw consumed (0 where none was): given back as ``uniforms=`` with the
+        same k they reproduce the draws
+    """
+
+    def __init__(self, T, k, seg_start, seg_state, logL, uniforms):
+        self.T = int(T)
+        self.k = np.asarray(k, dtype=np.int64)
+        self.seg_start = np.asarray(seg_start, dtype=np.int32)
+        self.seg_state = np.asarray(seg_state, dtype=np.int32)
+        self.logL = np.asarray(logL, dtype=np.float64)
+        self.uniforms = np.asarray(uniforms, dtype=np.float64)
+
+    def __len__(self):
+        return len(self.k)
+
+    def __repr__(self):
+        return f"ExactDraws(n={len(self.k)}, T={self.T}, k={np.unique(self.k).tolist()})"
+
+    @property
+    def n_switches(self):
+        return self.k
+
+    def states(self):
+        """ (n, T) int array: the state of every frame of every draw """
+        if len(self.k) == 0:
+            return np.zeros((0, self.T), dtype=int)
+        if np.any(self.seg_start[:, 0] < 0):
+            raise ValueError("a draw has no profile (no profile of positive weight with that many switches)")
+        return states_from_segments(self.seg_start, self.seg_state, self.T)
+
+    def profiles(self):
+        """ the draws as a list of `Loopingprofile` """
+        return [Loopingprofile(row) for row in self.states()]
+
+
+def _draw_k(r, n, k, dE, rng):
+    """ the (n,) switches of the draws of one result, every refusal included """
+    K = len(r.k)
+    ev = r.evidence
+    if k is None:
+        ks = np.full(n, r.best_k(dE), dtype=np.int64)
+    elif isinstance(k, str):
+        if k != 'average':
+            raise ValueError(f"k = {k!r}: None, an integer, an integer array of length n, or 'average'")
+        if np.any(np.isnan(ev)):
+            r.best_k(0)     # the warning, or the error when nothing is left
+        use = np.flatnonzero(np.isfinite(ev))
+        if len(use) == 0:
+            raise ValueError("no k has finite evidence")
+        with np.errstate(under='ignore'):
+            w = np.exp(ev[use] - np.max(ev[use]))
+        ks = use[rng.choice(len(use), size=n, p=w / np.sum(w))].astype(np.int64)
+    else:
+        a = np.asarray(k)
+        if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"k = {k!r}: None, an integer, an integer array of length n, or 'average'")
+        if a.ndim == 0:
+            ks = np.full(n, int(a), dtype=np.int64)
+        elif a.shape == (n,):
+            ks = a.astype(np.int64)
+        else:
+            raise ValueError(f"k has shape {a.shape}; an integer or ({n},) expected")
+    for kk in np.unique(ks):
+        if not 0 <= kk < K:
+            raise ValueError(f"k = {int(kk)}: the results hold k = 0 ... {K - 1}")
+        if np.isnan(ev[kk]):
+            raise ValueError(f"the evidence of k = {int(kk)} is NaN (a profile of {int(kk)} switches uses a NaN window): make the "
+                             f"results with nan='omit', which leaves such profiles out")
+        if ev[kk] == -np.inf:
+            raise ValueError(f"the evidence of k = {int(kk)} is -inf: no profile of {int(kk)} switches to draw")
+    return ks
+
+
+def exact_draw(results, n, k=None, dE=None, seed=0, uniforms=None, scratch_bytes=0):
+    """
+    n profiles per trajectory, drawn independently from the exact posterior over the profiles of k switches, by sampling
+    segment after segment against the backward tables of the segment recursion on the GPU: no
+    burn-in, no weights, no sampler error.
+
+    results : an `ExactSamplingResults` or a list of them over one model and one k_max; a list is served by ONE device call on
+        one trajectory set and gives a list of `ExactDraws`
+    n : draws per result
+    k : None -- `best_k(dE)` of each result; an int -- that k for every draw; an int array of length n -- each draw's own k
+        (replay uses this form; for a list of results also (len(results), n): each result's own); 'average' -- each draw's k is picked on the host with probability proportional to
+        exp(evidence_k) over the k of finite evidence, from ``np.random.default_rng(seed)`` (k with NaN evidence are left out
+        with `best_k`'s warning)
+    seed : of the device's uniforms (draw i of result j is stream j n + i), and of the host's choice of k under 'average'
+    uniforms : replay -- (n, max(1, 2 k_max)) uniforms in [0, 1), for a list of results (len(results), n, max(1, 2 k_max)):
+        `ExactDraws.uniforms` of an earlier call; ``seed`` is then not used by the device
+    scratch_bytes : device workspace of one chunk of whole trajectories (0: at most 1 GiB and a third of the free memory)
+
+    A k outside 0 ... k_max, or one whose evidence is -inf or NaN, raises ValueError; profiles that use a NaN window are never
+    drawn, so results made with nan='omit' give draws from the posterior without them.  Every refusal is raised before any
+    device work.  Returns an `ExactDraws` or a list of them.
+    """
+    single = isinstance(results, ExactSamplingResults)
+    items = [results] if single else list(results)
+    if any(not isinstance(r, ExactSamplingResults) for r in items):
+        raise TypeError("exact_draw needs ExactSamplingResults (from exact_sample) or a list of them")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError(f"n = {n!r}: a non-negative integer")
+    n = int(n)
+    if not items:
+        return []
+    model = items[0].model
+    K = len(items[0].k)
+    if any(r.model is not model for r in items):
+        raise ValueError("exact_draw needs results over one model")
+    if any(len(r.k) != K for r in items):
+        raise ValueError("exact_draw needs results of one k_max")
+    k_max, U = K - 1, max(1, 2 * (K - 1))
+    transitions = np.asarray(model.transitions, dtype=bool)
+    rng = np.random.default_rng(seed)
+    per_result = not single and not isinstance(k, str) and k is not None and np.ndim(k) == 2
+    if per_result and np.shape(k) != (len(items), n):
+        raise ValueError(f"k has shape {np.shape(k)}; an integer, ({n},) or ({len(items)}, {n}) expected")
+    ks = [_draw_k(r, n, np.asarray(k)[j] if per_result else k, dE, rng) for j, r in enumerate(items)]
+    if uniforms is not None:
+        uniforms = np.asarray(uniforms, dtype=np.float64)
+        want = (n, U) if single else (len(items), n, U)
+        if uniforms.shape != want:
+            raise ValueError(f"uniforms has shape {uniforms.shape}; {want} expected")
+        if not np.all((uniforms >= 0) & (uniforms < 1)):
+            raise ValueError("uniforms must lie in [0, 1) (NaN or a value outside given)")
+        uniforms = uniforms.reshape(len(items) * n, U)
+    if n == 0:
+        out = [ExactDraws(len(r.traj), ks[j], np.zeros((0, K), dtype=np.int32), np.zeros((0, K), dtype=np.int32), np.zeros(0),
+                          np.zeros((0, U))) for j, r in enumerate(items)]
+        return out[0] if single else out
+    ts = model.trajset(items[0].traj if single else [r.traj for r in items])
+    res = _lib.gauss_segment_draw(model.handle(), ts, k_max, transitions, np.repeat(np.arange(len(items)), n), np.concatenate(ks),
+                                  uniforms=uniforms, seed=seed, scratch_bytes=scratch_bytes)
+    out = [ExactDraws(len(r.traj), ks[j], res['seg_start'][j * n:(j + 1) * n], res['seg_state'][j * n:(j + 1) * n],
+                      res['logl'][j * n:(j + 1) * n], res['uniforms'][j * n:(j + 1) * n]) for j, r in enumerate(items)]
     return out[0] if single else out

@@ -881,6 +881,44 @@ typedef struct bild_segdp_out {
 int bild_gauss_segment_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k_max, const uint8_t *transitions,
                                 int T_max, unsigned flags, int64_t scratch_bytes, bild_segdp_out *out);
 
+/* ---------------------------------------------------------------- exact posterior draws of profiles ----
+ * GenericGaussianModel only.  Independent draws from the exact posterior over the profiles of k
+ * switches (the profiles and the uniform prior of the segment recursion above), by sampling a profile segment by segment
+ * from the left against the backward tables of that recursion.  Draw r belongs to trajectory draw_traj[r] of the set and
+ * has draw_k[r] switches (0 .. k_max); it consumes a row of U = max(1, 2 k_max) uniforms in [0, 1):
+ *   u[0]       (s_0, t_1) jointly, the list ordered by state, then by the end frame b = 1 .. T, weights
+ *              exp F[s][b] gamma_k(b, s) (gamma_m(b, s): the sum over the completions, m switches to come, of a profile
+ *              whose segment in state s ends at b)
+ *   u[2i - 1]  s_i among the q with transitions[s_{i-1}, q], ascending, weights beta_{k-i}(t_i, q) (beta_m(a, s) =
+ *              sum_{b > a} exp W[s][a - 1][b] gamma_m(b, s)), for i = 1 .. k
+ *   u[2i]      t_{i+1} among b = t_i + 1 .. T, ascending, weights exp W[s_i][t_i - 1][b] gamma_{k-i}(b, s_i), for i < k; the
+ *              last segment ends at T and takes no uniform.
+ * A pick returns the first entry of positive weight whose inclusive running weight exceeds u times the list's total, and the
+ * last entry of positive weight where rounding carries that product past the end; an entry of weight 0 -- a NaN window
+ * ("Deviation") or a term of -inf -- is never returned, so a NaN profile is never drawn.  A pick with
+ * one candidate still consumes its uniform.  With K = k_max + 1, per draw:
+ *   seg_start, seg_state  draw_k[r] + 1 segments, the rest of the row of K entries padded with empty segments at T in
+ *                         state 0; -1 everywhere: the trajectory has no profile of positive weight with that many switches
+ *   logl                  F[s_0][t_1] + sum_i W[s_i][t_i - 1][t_{i+1}], added from the left as bild_gauss_logl_segments adds
+ *                         it; NaN for a -1 row
+ *   uniforms_out          (may be NULL) the uniforms the draw consumed, in the layout of `uniforms`; 0 where none was
+ * Replay: `uniforms` (n_draws x U) is given and `seed` ignored.  Device: uniforms == NULL; the uniforms of draw r are the
+ * Philox-4x32-10 stream (key: seed; counter: r) taken in the order above, so a draw is a pure function of (seed, r, its
+ * trajectory's tables, its k, transitions).  Results do not depend on the other draws, on the set's other trajectories or
+ * their order, or on scratch_bytes (chunks of whole trajectories as in bild_gauss_segment_evidence; trajectories that no draw
+ * names are skipped).  Refused before any device work: what bild_gauss_segment_evidence refuses, n_draws < 0, a draw_traj
+ * or draw_k out of range, a uniform outside [0, 1) or NaN (BILD_ERR_INVALID).  n_draws = 0 returns at once.  Plain
+ * launches on the set's stream, no atomics.  Synchronous. */
+typedef struct bild_segdraw_out {
+    int32_t *seg_start, *seg_state;         /* n_draws x K */
+    double *logl;                           /* n_draws */
+    double *uniforms_out;                   /* n_draws x U, or NULL */
+} bild_segdraw_out;
+
+int bild_gauss_segment_draw(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k_max, const uint8_t *transitions,
+                            int T_max, int64_t scratch_bytes, int64_t n_draws, const int32_t *draw_traj, const int32_t *draw_k,
+                            const double *uniforms, uint64_t seed, bild_segdraw_out *out);
+
 #ifdef __cplusplus
 }
 #endif
