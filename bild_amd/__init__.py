@@ -15,6 +15,7 @@ from .core import sample, sample_many, SamplingResults, posterior_distances  # n
 from .models import MultiStateModel, MultiStateRouse, FactorizedModel, KalmanResult, FitResult  # noqa: F401
 from .gauss import GenericGaussianModel  # noqa: F401
 from .exact import exact_evidence, ExactResult, exact_sample, ExactSamplingResults, exact_draw, ExactDraws  # noqa: F401
+from .exact import exact_sensitivities, EvidenceSensitivities  # noqa: F401
 from .amis import FixedkSampler, Dirichlet, CFC  # noqa: F401
 from .profiles import Loopingprofile  # noqa: F401
 from .trajectory import Trajectory  # noqa: F401

@@ -167,6 +167,9 @@ _SIGNATURES = {
     # exact posterior draws from the segment recursion's backward tables (gauss_segdraw.cpp)
     'bild_gauss_segment_draw': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _ip, _ip, _dp,
                                                ctypes.c_uint64, _vp]),
+    # gradient of the exact evidence with respect to model parameters (gauss_segsens.cpp)
+    'bild_gauss_segment_sensitivities': (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, _vp, ctypes.c_uint, _dp, ctypes.c_int, _vp,
+                                                        ctypes.c_int64, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1307,4 +1310,41 @@ def gauss_segment_draw(model, ts, k_max, transitions, draw_traj, draw_k, uniform
     check(lib().bild_gauss_segment_draw(model._h, ts._h, int(k_max), aptr(tr), int(np.max(ts.T)), int(scratch_bytes), n, iptr(draw_traj),
                                         iptr(draw_k), None if uniforms is None else aptr(uniforms), int(seed) & (2 ** 64 - 1),
                                         ctypes.byref(spec)))
+    return res
+
+
+class SegsensOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'log_marginal', 'k_post', 'grad', 'exp_logl', 'fisher')]
+
+
+def gauss_segment_sensitivities(model, ts, trajs, k_max, transitions, log_k_prior=None, dmsd=None, dmsd_inf=None, dmean=None, P=0,
+                                omit=False, fisher=True, scratch_bytes=0):
+    """
+    gradient of the exact evidence of every trajectory of the set (bild_gauss_segment_sensitivities): trajs the (T, d) arrays
+    the set was built from, log_k_prior None or (n_traj, K), derivatives as for `gauss_logl_sensitivities`.  A dict of logev,
+    k_post (n_traj, K), log_marginal, exp_logl (n_traj,), grad (n_traj, P) and fisher (n_traj, P, P) or None; K = k_max + 1
+    """
+    tr = _transitions_u8(transitions, model.S)
+    n, K = ts.n_traj, int(k_max) + 1
+    arrs = [f64(t) for t in trajs]
+    assert len(arrs) == n and all(len(a) == T for a, T in zip(arrs, ts.T))
+    x = f64(np.concatenate(arrs, axis=0))
+    prior = None
+    if log_k_prior is not None:
+        prior = f64(log_k_prior)
+        assert prior.shape == (n, K)
+    S, d, L1 = model.S, model.d, model.Tmax + 1
+    keep = {}
+    for name, a, shape in (('dmsd', dmsd, (P, S, d, L1)), ('dmsd_inf', dmsd_inf, (P, S, d)), ('dmean', dmean, (P, S, d))):
+        if a is not None:
+            a = f64(a)
+            assert a.shape == shape, f"{name} has shape {a.shape}, expected {shape}"
+            keep[name] = a
+    derivs = GaussDerivs(**{k: aptr(a) if a.size else None for k, a in keep.items()})
+    res = {'logev': np.empty((n, K)), 'log_marginal': np.empty(n), 'k_post': np.empty((n, K)), 'grad': np.empty((n, P)),
+           'exp_logl': np.empty(n), 'fisher': np.empty((n, P, P)) if fisher else None}
+    spec = SegsensOut(**{name: (aptr(a) if a is not None and a.size else None) for name, a in res.items()})
+    check(lib().bild_gauss_segment_sensitivities(model._h, ts._h, dptr(x), int(k_max), aptr(tr), SEGDP_NAN_OMIT if omit else SEGDP_NAN_PROPAGATE,
+                                                 None if prior is None else dptr(prior), int(P), ctypes.byref(derivs),
+                                                 int(scratch_bytes), ctypes.byref(spec)))
     return res

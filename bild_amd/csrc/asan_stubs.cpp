@@ -97,3 +97,9 @@ namespace bild {
 int launch_segdraw_head(const SegdrawParams &, void *) { return 1; }
 int launch_segdraw(const SegdrawParams &, const SegdrawParams *, void *) { return 1; }
 } // namespace bild
+#include "gauss_segsens.h"
+namespace bild {
+int launch_segsens_weight(const SegdpParams &, const SegsensWeights &, void *) { return 1; }
+int launch_segsens_solve(const GaussSensSet *, const SegsensJob *, int, int, int, const double *, double *, void *) { return 1; }
+int launch_segsens_factor(const GaussSensSet *, const SegsensJob *, int, int, const double *, double *, double *, void *) { return 1; }
+} // namespace bild

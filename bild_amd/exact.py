@@ -441,3 +441,87 @@ def exact_draw(results, n, k=None, dE=None, seed=0, uniforms=None, scratch_bytes
     out = [ExactDraws(len(r.traj), ks[j], res['seg_start'][j * n:(j + 1) * n], res['seg_state'][j * n:(j + 1) * n],
                       res['logl'][j * n:(j + 1) * n], res['uniforms'][j * n:(j + 1) * n]) for j, r in enumerate(items)]
     return out[0] if single else out
+
+
+# ---------------------------------------------------------------- gradient of the exact evidence (section 20)
+
+class EvidenceSensitivities:
+    """
+    `exact_sensitivities` of n trajectories, K = k_max + 1 and P parameters:
+
+    log_marginal : (n,) log sum_k pi_k ev_k, pi the normalised prior over k
+    k_posterior : (n, K) pi_k ev_k / sum pi ev
+    logev : (n, K) the log evidence of every k, the numbers `exact_sample` gives
+    grad : (n, P) the gradient of ``log_marginal`` with respect to the parameters
+    expected_logL : (n,) the posterior mean of the log-likelihood
+    fisher : (n, P, P) or None; the posterior mean of the complete-data information (innovations form).  A scoring matrix:
+        the information of the marginal likelihood is smaller, so it does not give standard errors.
+
+    A trajectory whose evidence is NaN at a k of positive prior weight (``nan='propagate'``) is NaN in all but ``logev``.
+    """
+
+    __slots__ = ('log_marginal', 'k_posterior', 'logev', 'grad', 'expected_logL', 'fisher')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return f"EvidenceSensitivities(n={len(self.log_marginal)}, K={self.logev.shape[1]}, P={self.grad.shape[1]})"
+
+
+def _log_k_prior(k_prior, n, K):
+    """ `exact_sensitivities`' k_prior -> None or (n, K) log weights, checked """
+    if k_prior is None:
+        return None
+    if isinstance(k_prior, (int, np.integer)) and not isinstance(k_prior, bool):
+        if not 0 <= k_prior < K:
+            raise ValueError(f"k_prior = {k_prior}: a single k must lie in 0 ... {K - 1}")
+        w = np.zeros(K)
+        w[int(k_prior)] = 1.0
+    else:
+        w = np.asarray(k_prior, dtype=np.float64)
+    if w.shape not in ((K,), (n, K)):
+        raise ValueError(f"k_prior has shape {w.shape}; None, an integer, ({K},) or ({n}, {K}) expected")
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("k_prior must be finite and non-negative")
+    w = np.broadcast_to(w, (n, K))
+    if np.any(w.sum(axis=1) <= 0):
+        raise ValueError("k_prior is zero everywhere for a trajectory")
+    with np.errstate(divide='ignore'):
+        return np.ascontiguousarray(np.log(w))
+
+
+def exact_sensitivities(trajs, model, dmsd=None, dmsd_inf=None, dmean=None, k_max=20, k_prior=None, nan='propagate', fisher=True,
+                        scratch_bytes=0):
+    """
+    The gradient of the exact evidence of `exact_sample` with respect to P <= 4 model parameters, for trajectories whose
+    looping profile is not known (bild_gauss_segment_sensitivities).  By Fisher's identity it is the
+    posterior mean over all profiles of the gradient of the log-likelihood; the posterior weights of the segments come from
+    the segment recursion, the gradients from forward tangents of every window's Cholesky factor.  No sampler, no noise.
+
+    trajs : a trajectory or a list of them (one device call)
+    model : a `GenericGaussianModel` (anything else: TypeError)
+    dmsd, dmsd_inf, dmean : the derivatives of the model's tables, as `GenericGaussianModel.logL_sensitivities` takes them
+    k_max : largest number of switches, 0 <= k_max <= 64
+    k_prior : the prior over k.  None: uniform on 0 ... k_max; an integer: that k alone; (K,) or (n_traj, K) non-negative
+        weights (normalised here).  A k of weight 0 is skipped.
+    nan : as for `exact_sample`.  Under 'propagate' a trajectory with a NaN evidence at a k of positive weight is NaN.
+    fisher : return the posterior-weighted Fisher matrix
+    scratch_bytes : device workspace of one chunk (0: the library's rule)
+
+    Every refusal is raised before the trajectories are uploaded.  Returns `EvidenceSensitivities`.
+    """
+    single, items, transitions = _check_exact_sample(trajs, model, k_max, nan)
+    P, given = model._derivative_arrays(dmsd, dmsd_inf, dmean)
+    K = int(k_max) + 1
+    prior = _log_k_prior(k_prior, len(items), K)
+    if not items:
+        return EvidenceSensitivities(log_marginal=np.zeros(0), k_posterior=np.zeros((0, K)), logev=np.zeros((0, K)),
+                                     grad=np.zeros((0, P)), expected_logL=np.zeros(0), fisher=np.zeros((0, P, P)) if fisher else None)
+    arrs = model._direct_arrays(items)
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_segment_sensitivities(model.handle(), ts, arrs, int(k_max), transitions, log_k_prior=prior, P=P,
+                                           omit=nan == 'omit', fisher=fisher, scratch_bytes=scratch_bytes, **given)
+    return EvidenceSensitivities(log_marginal=res['log_marginal'], k_posterior=res['k_post'], logev=res['logev'], grad=res['grad'],
+                                 expected_logL=res['exp_logl'], fisher=res['fisher'])

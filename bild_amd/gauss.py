@@ -233,6 +233,13 @@ class GenericGaussianModel(MultiStateModel):
         Returns (logL (n,), grad (n, P), fisher (n, P, P) or None); NaN rows where `logL_segments` gives NaN.
         """
         items, seg_start, seg_state, tid = self._kalman_args(profiles, trajs, traj_id)
+        P, given = self._derivative_arrays(dmsd, dmsd_inf, dmean)
+        arrs = self._direct_arrays(items)
+        return _lib.gauss_logl_sensitivities(self.handle(), arrs, seg_start, seg_state, tid, P=P, fisher=fisher,
+                                             scratch_bytes=scratch_bytes, **given)
+
+    def _derivative_arrays(self, dmsd, dmsd_inf, dmean):
+        """ the derivative arrays of a sensitivities call, checked on the host: -> (P, dict of the arrays given) """
         S, d, n_lags = self.msd.shape
         given = {}
         for name, a, tail in (('dmsd', dmsd, (S, d, n_lags)), ('dmsd_inf', dmsd_inf, (S, d)), ('dmean', dmean, (S, d))):
@@ -251,11 +258,9 @@ class GenericGaussianModel(MultiStateModel):
         for name, a in given.items():
             if not np.all(np.isfinite(a)):
                 raise ValueError(f"{name} is not finite everywhere")
-        arrs = self._direct_arrays(items)
         if 'dmsd' in given:     # the library's tables end at lag Tmax = n_lags - 1, as the model handle's do
             given['dmsd'] = given['dmsd'][..., :n_lags]
-        return _lib.gauss_logl_sensitivities(self.handle(), arrs, seg_start, seg_state, tid, P=P, fisher=fisher,
-                                             scratch_bytes=scratch_bytes, **given)
+        return P, given
 
     def _direct_arrays(self, items):
         """ the (T, d) arrays of trajectories that a call takes directly (no trajectory set), checked on the host """
@@ -377,6 +382,78 @@ class GenericGaussianModel(MultiStateModel):
             return model, float(logl.sum()), g.sum(axis=0), F.sum(axis=0)
 
         return _fisher_scoring(evaluate, theta, params, tol, max_iter)
+
+    @classmethod
+    def fit_marginal(cls, trajs, family, start, derivatives=None, k_max=20, k_prior=None, nan='propagate', tol=1e-8, max_iter=50):
+        """
+        Maximum-likelihood fit of positive parameters theta on trajectories whose looping profiles are NOT known: the
+        objective is the sum over the trajectories of the exact log marginal likelihood log sum_k pi_k p(traj | theta, k)
+        (`bild_amd.exact_sensitivities`), every profile of up to ``k_max`` switches summed over.
+
+        trajs, family, start, derivatives, tol, max_iter : as for `fit`
+        k_max, k_prior, nan : as for `bild_amd.exact_sensitivities`
+
+        Each evaluation builds the model of the trial theta, its trajectory set, and makes one `exact_sensitivities` call.
+        The steps are Fisher scoring in log theta with the posterior mean of the complete-data information as the
+        matrix (`fit`'s stopping rule and damping); that matrix overstates the information of the marginal likelihood,
+        so the standard errors come from the observed information instead: central differences in log theta (step 1e-4)
+        of the exact gradient at the optimum, symmetrised -- 2 P further evaluations, counted in ``n_iter``.  ``cov`` and
+        ``se`` follow from its pseudo-inverse by the delta method; ``logL`` holds the total log marginal.
+        """
+        from .exact import exact_sensitivities, _check_exact_sample, _log_k_prior
+        start = dict(start)
+        params = tuple(start)
+        if not params:
+            raise ValueError("nothing to fit: start is empty")
+        if len(params) > 4:
+            raise ValueError("at most 4 parameters")
+        theta = np.array([float(start[p]) for p in params])
+        if np.any(~np.isfinite(theta)) or np.any(theta <= 0):
+            raise ValueError(f"parameters must be positive and finite: {start}")
+        if tol <= 0 or max_iter < 1:
+            raise ValueError("need tol > 0 and max_iter >= 1")
+        items = list(trajs) if isinstance(trajs, (list, tuple)) else [trajs]
+        if not items:
+            raise ValueError("need at least one trajectory")
+        probe = cls(family(**dict(zip(params, theta))))
+        _check_exact_sample(items, probe, k_max, nan)
+        _log_k_prior(k_prior, len(items), int(k_max) + 1)
+
+        def evaluate(th):
+            kw = dict(zip(params, th))
+            model = cls(family(**kw))
+            if derivatives is not None:
+                dmsd, dmsd_inf, dmean = derivatives(**kw)
+            else:
+                dmsd, dmsd_inf, dmean = _log_differences(cls, family, params, th)
+            r = exact_sensitivities(items, model, dmsd=dmsd, dmsd_inf=dmsd_inf, dmean=dmean, k_max=k_max, k_prior=k_prior, nan=nan)
+            g, F = _log_chain_rule(r.grad, r.fisher, np.broadcast_to(th, r.grad.shape))
+            return model, float(r.log_marginal.sum()), g.sum(axis=0), F.sum(axis=0)
+
+        first = evaluate(theta)
+        if np.isnan(first[1]):
+            hint = " (a trajectory has a NaN evidence: a later ss_order-0 segment without a valid frame; try nan='omit')" \
+                if nan == 'propagate' else ""
+            raise ValueError(f"the log marginal likelihood is NaN at the start{hint}")
+        calls = [first]
+
+        def cached(th):     # the start is evaluated once
+            return calls.pop() if calls else evaluate(th)
+
+        res = _fisher_scoring(cached, theta, params, tol, max_iter)
+        th = np.array([res.params[p] for p in params])
+        P, h = len(params), _MARGINAL_INFO_STEP
+        H = np.zeros((P, P))
+        for p in range(P):
+            e = np.zeros(P)
+            e[p] = h
+            H[:, p] = -(evaluate(th * np.exp(e))[2] - evaluate(th * np.exp(-e))[2]) / (2 * h)
+        H = 0.5 * (H + H.T)
+        cov = np.linalg.pinv(H) * np.outer(th, th)
+        res.cov = cov
+        res.se = dict(zip(params, np.sqrt(np.maximum(np.diag(cov), 0.))))
+        res.n_iter += 2 * P
+        return res
 
     # ------------------------------------------------------------------ generative model
     def trajectory_from_loopingprofile(self, profile, missing_frames=None, rng=None):
@@ -509,6 +586,7 @@ class GenericGaussianModel(MultiStateModel):
 
 
 _LOG_STEP = 1e-5
+_MARGINAL_INFO_STEP = 1e-4      # fit_marginal: step in log theta of the observed information's central differences
 
 
 def _log_differences(cls, family, params, theta, h=_LOG_STEP):

@@ -919,6 +919,49 @@ int bild_gauss_segment_draw(const bild_gauss_model *m, const bild_gauss_trajset 
                             int T_max, int64_t scratch_bytes, int64_t n_draws, const int32_t *draw_traj, const int32_t *draw_k,
                             const double *uniforms, uint64_t seed, bild_segdraw_out *out);
 
+/* ---------------------------------------------------------------- evidence sensitivities ----
+ * GenericGaussianModel only.  The gradient of the exact evidence of the segment recursion above with
+ * respect to P <= 4 model parameters, for trajectories whose profile is not known.  With ev_k = exp(logev_k) of
+ * bild_gauss_segment_evidence (same k_max, transitions and NaN flag; the same numbers, bit for bit) and a prior over k,
+ * pi_k proportional to exp(log_k_prior[k]) (a row of K = k_max + 1 per trajectory, finite or -inf; NULL: uniform), per
+ * trajectory:
+ *   logev          K values, as bild_gauss_segment_evidence gives them
+ *   log_marginal   log sum_k pi_k ev_k, pi normalised over k = 0 .. k_max
+ *   k_post         K values: pi_k ev_k / sum pi ev
+ *   grad           P values: d log_marginal / d theta_p.  By Fisher's identity it is the posterior mean of the gradient of the
+ *                  log-likelihood: with Omega(s, a, t) the posterior probability (k mixed by k_post) that a segment in
+ *                  state s starts at a and has not ended by frame t, grad_p = - sum Omega(s, a, t_j) dtau_p over the
+ *                  entries j of the window that starts at a - 1 (the first window for a = 0), tau and dtau those of
+ *                  bild_gauss_logl_sensitivities.
+ *   exp_logl       - sum Omega tau: the posterior mean of the log-likelihood (one k: kl + logev of that k)
+ *   fisher         P x P: sum Omega (2 a_p a_q + g_p g_q), the innovations form
+ *                  of bild_gauss_logl_sensitivities, posterior-weighted.  This is the posterior mean of the complete-data
+ *                  information: a scoring matrix for a fit.  It is NOT the information of the marginal likelihood, which
+ *                  is smaller by the posterior covariance of the score; standard errors need the latter.
+ * The trajectories' data are given as bild_gauss_simulate returns them (x: sum T x d in the set's order, NaN = missing);
+ * they must be the data the set was built from.  Derivatives as for bild_gauss_logl_sensitivities.  A k of prior weight 0
+ * is skipped, NaN or not.  flags = 0: a trajectory with a k of positive prior weight whose logev is NaN has NaN in
+ * log_marginal, k_post, grad, exp_logl and fisher; the other trajectories are untouched.  A trajectory without a profile
+ * of positive weight under the prior has log_marginal -inf and NaN in the rest.  NULL outputs are not written.  No
+ * atomics, fixed summation orders that depend on the trajectory alone: results are bit-identical across calls, the order
+ * of the set, a trajectory alone or in a batch, and scratch_bytes (chunks of whole trajectories, and of factorisations
+ * of windows with a missing frame; 0: at most 1 GiB and a third of the free device memory).  tau sums do not depend on P.
+ * Refused before any device work: what bild_gauss_segment_evidence and bild_gauss_logl_sensitivities refuse, a NaN or
+ * +inf log_k_prior entry, a log_k_prior row that is -inf everywhere (BILD_ERR_INVALID).  Plain launches on the set's
+ * stream.  Synchronous. */
+typedef struct bild_segsens_out {
+    double *logev;                          /* n_traj x K */
+    double *log_marginal;                   /* n_traj */
+    double *k_post;                         /* n_traj x K */
+    double *grad;                           /* n_traj x P */
+    double *exp_logl;                       /* n_traj */
+    double *fisher;                         /* n_traj x P x P */
+} bild_segsens_out;                         /* every pointer may be NULL: not written */
+
+int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const bild_gauss_trajset *ts, const double *x, int k_max,
+                                     const uint8_t *transitions, unsigned flags, const double *log_k_prior, int P,
+                                     const bild_gauss_derivs *dm, int64_t scratch_bytes, bild_segsens_out *out);
+
 #ifdef __cplusplus
 }
 #endif
