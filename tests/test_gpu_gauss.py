@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import gauss_oracle as G
+from gauss_table_cases import model_from, random_case
 
 pytestmark = pytest.mark.gpu
 
@@ -20,31 +21,6 @@ GOLDENS = sorted(glob.glob(os.path.join(HERE, 'golden', 'gauss', '*.npz')))
 def load(path):
     z = np.load(path)
     return {k: z[k] for k in z.files}
-
-
-def model_from(msd, msd_inf, mean, order):
-    import bild_amd
-    S, d = order.shape
-    return bild_amd.GenericGaussianModel(
-        [[(msd[n, k] if order[n, k] == 1 else np.append(msd[n, k], msd_inf[n, k]), mean[n, k], int(order[n, k]))
-          for k in range(d)] for n in range(S)])
-
-
-def random_case(rng, S, d, T, p_missing):
-    lags = np.arange(T, dtype=float)
-    msd = np.zeros((S, d, T))
-    inf = np.zeros((S, d))
-    for n in range(S):
-        for k in range(d):
-            G_, a, s2 = rng.uniform(0.3, 2), rng.uniform(0.4, 1.2), rng.uniform(0.05, 0.3)
-            msd[n, k] = np.where(lags > 0, G_ * lags ** a + 2 * s2, 0)
-            inf[n, k] = 2 * G_ * T ** a + 4 + 2 * s2
-    order = rng.integers(0, 2, size=(S, d))
-    mean = rng.normal(scale=0.3, size=(S, d))
-    x = np.cumsum(rng.normal(size=(T, d)), axis=0)
-    if p_missing:
-        x[rng.random((T, d)) < p_missing] = np.nan
-    return msd, inf, mean, order, x
 
 
 def random_states(rng, n, T, S, kmax=6):
