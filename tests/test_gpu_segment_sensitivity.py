@@ -26,14 +26,14 @@ def rel(got, want):
     return 0.0 if want.size == 0 else float(np.max(np.abs(got - want))) / (scale if scale > 0 else 1.0)
 
 
-def check_against_oracle(model, x, k_max, nan, k_prior=None, label=''):
-    """ P = 0 ... 4 on one trajectory against the oracle (computed once at P = 4); returns the worst relative deviation """
+def check_against_oracle(model, x, k_max, nan, k_prior=None, label='', want=None):
+    """
+    P = 0 ... 4 on one trajectory against the oracle (computed once at P = 4, or given as `want`); returns the worst relative
+    deviation
+    """
     K = k_max + 1
-    lp = None
-    if k_prior is not None:
-        with np.errstate(divide='ignore'):      # (an integer: that k alone)
-            lp = np.log(np.arange(K) == k_prior if isinstance(k_prior, int) else np.asarray(k_prior, dtype=float))
-    want = SC.oracle(model, x, k_max, P=4, log_k_prior=lp, nan=nan)
+    if want is None:
+        want = SC.oracle(model, x, k_max, P=4, log_k_prior=SC.log_prior(k_prior, K), nan=nan)      # (an integer: that k alone)
     ref = bild_amd.exact_sample(x, model, k_max=k_max, marginals=False, nan=nan)
     worst, base = 0.0, None
     for P in range(5):
@@ -82,21 +82,13 @@ def test_short_trajectories(T):
     assert np.all(r.k_posterior[0, T:] == 0) and np.all(r.logev[0, T:] == -np.inf)
 
 
-def order0_gap_case(rng, T):
-    model = bild_amd.GenericGaussianModel([[(np.append(np.arange(T + 8) * 0.5 + 0.1, 50.0), 0.3 * s, 0),
-                                            (np.arange(T + 8) * (0.5 + s), 0.0, 1)] for s in range(2)])
-    x = C.random_traj(rng, T)
-    x[20:26, 0] = np.nan        # a later ss_order-0 segment inside frames 20 .. 25 has no valid value in dimension 0
-    return model, x
-
-
 @pytest.mark.parametrize('case', ['s2_gapfree', 's3_gapfree', 's2_inner_gap', 's3_leading_and_inner_gap', 's2_order0_gap'])
 def test_against_oracle_k12(case):
     S = int(case[1])
     rng = np.random.default_rng(sum(map(ord, case)))
     T = 60 if S == 2 else 52
     if 'order0' in case:
-        model, x = order0_gap_case(rng, 56)
+        model, x = SC.order0_gap_case(rng, 56)
         check_against_oracle(model, x, 12, 'propagate', label=case)                  # NaN: k >= 2 has NaN profiles
         check_against_oracle(model, x, 12, 'propagate', k_prior=[1, 1] + [0] * 11, label=case + ' k<=1')
         check_against_oracle(model, x, 12, 'omit', label=case)
@@ -228,7 +220,7 @@ def test_bit_identity_across_calls_orders_batches_and_scratch():
 
 def test_nan_trajectory_alone():
     rng = np.random.default_rng(3)
-    model, bad = order0_gap_case(rng, 56)
+    model, bad = SC.order0_gap_case(rng, 56)
     good = [C.random_traj(rng, 50), C.random_traj(rng, 56)]
     dmsd, dinf, dmean = SC.derivatives(model, 3)
     kw = dict(dmsd=dmsd, dmsd_inf=dinf, dmean=dmean, k_max=5)

@@ -1,8 +1,11 @@
 """
 The evidence gradient without a GPU (bild_amd.exact.exact_sensitivities): the NumPy oracle
 tests/segment_sensitivity_oracle.py against central differences of the segment recursion's log evidence and against the
-enumeration of every profile, its identities, and the argument errors of `exact_sensitivities` and `fit_marginal`.
+enumeration of every profile, its identities, the argument errors of `exact_sensitivities` and `fit_marginal`, and the designed
+cases of tests/test_gpu_segment_sensitivity_tiles.py: that they build, where their evidence is NaN, and the k = 0 identity.
 """
+import os
+
 import numpy as np
 import pytest
 from scipy import stats
@@ -179,3 +182,85 @@ def test_fit_marginal_refusals_before_device(built_lib):
     with pytest.raises(ValueError, match='single k'):
         fit([x], family, dict(a=1.0), k_max=3, k_prior=4)
     assert len(made) <= 9       # one probe model per call at the most: no trajectory set, no evaluation
+
+
+# ---------------------------------------------------------------- the designed cases of the GPU tier (beyond one 64-frame tile)
+
+def test_designed_cases_build():
+    assert len(SC.DESIGNED) == 14
+    for name, (mname, T, missing, k_max, runs) in SC.DESIGNED.items():
+        model, x, k = SC.designed(name)
+        d = model.msd.shape[1]
+        assert x.shape == (T, d) and k == k_max and T > 63 and model.msd.shape[2] >= T and len(runs) >= 1
+        assert SC.designed(name)[1] is x and not x.flags.writeable          # built once, shared, left unchanged
+        if mname is not None:
+            assert model is SC.designed_model(mname)                        # cases of one model can form a batch
+            gone = np.zeros(T, dtype=bool)
+            gone[list(missing)] = True
+            assert np.array_equal(np.isnan(x), np.repeat(gone[:, None], d, axis=1))
+        for p in range(5):
+            assert [a.shape[0] for a in SC.derivatives(model, p)] == [p] * 3
+    # what the cases aim at
+    S, d = SC.designed_model('edge').ss_order.shape
+    assert (S, d) == (2, 2) and SC.designed_model('edge').ss_order.tolist() == [[0, 1], [1, 0]]
+    straddle = SC.designed_model('straddle')
+    assert straddle.nStates == 3 and not straddle.transitions[0, 2] and np.all(straddle.ss_order == 1)
+    assert set(SC.STRADDLE_MISSING) >= {0, 62, 63, 64, 65, 127} and np.isnan(SC.designed('straddle_T128')[1][-1]).all()
+    model, x, _ = SC.designed('order0_gap_T130')
+    assert model.ss_order.tolist() == [[0, 1], [0, 1]] and np.array_equal(np.nonzero(np.isnan(x[:, 0]))[0], np.arange(61, 67))
+    assert not np.isnan(x[:, 1]).any()
+    assert SC.designed_model('d3').msd.shape[1] == 3 and SC.designed_model('d1_S4').msd.shape[:2] == (4, 1)
+    assert np.all(SC.designed_model('d1_S4').transitions == ~np.eye(4, dtype=bool))
+    for o in (0, 1):        # solve jobs of 260 / 259 entries, factorisations of 260 / 259 rows: the 256-thread stride wraps
+        model = SC.designed_model(f'stride_o{o}')
+        assert np.all(model.ss_order == o) and model.msd.shape[:2] == (2, 1)
+        assert 260 - o > 256 and (259 - o) + 1 > 256
+
+
+@pytest.mark.parametrize('name', list(SC.DESIGNED))
+def test_designed_cases_nan_condition(name):
+    """ the oracle's logev is finite at every k, except `order0_gap_T130` under 'propagate': there exactly k >= 2 is NaN """
+    k_max = SC.DESIGNED[name][3]
+    for nan in sorted({nan for _, nan, _ in SC.designed_runs([name])}):
+        logev = SC.designed_logev(name, nan)
+        assert logev.shape == (k_max + 1,)
+        if (name, nan, None) in SC.NAN_RUNS:
+            assert np.all(np.isfinite(logev[:2])) and np.all(np.isnan(logev[2:]))
+        else:
+            assert np.all(np.isfinite(logev)), (name, nan, logev)
+    assert {n for n, _, _ in SC.NAN_RUNS} == {'order0_gap_T130'}
+    for n, nan, prior in SC.designed_runs([name]):      # a prior run of a NaN case puts no weight on the NaN ks
+        if prior is not None and (n, nan, None) in SC.NAN_RUNS:
+            assert np.all(np.isfinite(SC.designed_logev(n, nan)[np.asarray(prior) > 0]))
+
+
+def test_k0_identity_with_the_flat_profiles():
+    """ all prior weight on k = 0: the segment oracle against the softmax-weighted flat profiles of the tangent oracle """
+    rng = np.random.default_rng(70)
+    lags = np.arange(78, dtype=float)
+    msd = np.where(lags > 0, 0.9 * lags ** 0.8 + 0.2, 0.0)
+    # two states a little apart, so that both flat profiles keep weight; dimension 0 of ss_order 0, dimension 1 of ss_order 1
+    model = bild_amd.GenericGaussianModel([[(np.append(c * msd, c * 80.0), m, 0), (c * msd, m, 1)] for c, m in ((1.0, 0.05), (1.15, -0.1))])
+    x = C.random_traj(rng, 70, (33,))
+    got = SC.oracle(model, x, 2, P=4, log_k_prior=SC.log_prior(0, 3), nan='omit')
+    want = SC.flat_profile_reference(model, x)
+    assert np.min(want['weights']) > 1e-3
+    devs = {'log_marginal': abs(got['log_marginal'] - want['log_marginal']) / abs(want['log_marginal']),
+            'exp_logl': abs(got['exp_logl'] - want['exp_logl']) / abs(want['exp_logl']),
+            'grad': np.max(np.abs(got['grad'] - want['grad'])) / np.max(np.abs(want['grad'])),
+            'fisher': np.max(np.abs(got['fisher'] - want['fisher'])) / np.max(np.abs(want['fisher']))}
+    print(f"k = 0 identity at T = 70: {devs}, weights {want['weights']}")
+    assert max(devs.values()) < 1e-12, devs
+    assert np.array_equal(got['k_post'], [1.0, 0.0, 0.0])
+
+
+@pytest.mark.skipif(not os.environ.get('BILD_DESIGNED_ORACLE'), reason="runs the oracle on every designed case (about 90 s): "
+                    "set BILD_DESIGNED_ORACLE=1; the GPU tier asserts the same limit on every answer it uses")
+@pytest.mark.parametrize('name,nan,prior', SC.designed_runs())
+def test_designed_oracle_answers_take_under_20s(name, nan, prior):
+    out = SC.designed_oracle(name, nan, prior)
+    seconds = SC.ORACLE_SECONDS[name, nan, prior]
+    print(f"{name} {nan} {prior}: {seconds:.1f} s")
+    assert seconds < 20.0
+    assert np.array_equal(out['logev'], SC.designed_logev(name, nan), equal_nan=True)
+    assert np.isnan(out['log_marginal']) == ((name, nan, prior) in SC.NAN_RUNS)
