@@ -170,6 +170,9 @@ _SIGNATURES = {
     # gradient of the exact evidence with respect to model parameters (gauss_segsens.cpp)
     'bild_gauss_segment_sensitivities': (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, _vp, ctypes.c_uint, _dp, ctypes.c_int, _vp,
                                                         ctypes.c_int64, _vp]),
+    # exact inference under a dwell-time prior (gauss_dwell.cpp)
+    'bild_gauss_dwell_evidence': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_uint, ctypes.c_int64,
+                                                 _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1347,4 +1350,34 @@ def gauss_segment_sensitivities(model, ts, trajs, k_max, transitions, log_k_prio
     check(lib().bild_gauss_segment_sensitivities(model._h, ts._h, dptr(x), int(k_max), aptr(tr), SEGDP_NAN_OMIT if omit else SEGDP_NAN_PROPAGATE,
                                                  None if prior is None else dptr(prior), int(P), ctypes.byref(derivs),
                                                  int(scratch_bytes), ctypes.byref(spec)))
+    return res
+
+
+class DwellOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'map_logjoint', 'map_states', 'n_nan_windows', 'log_post', 'exp_jumps',
+                                                      'exp_stay')]
+
+
+DWELL_NAN_PROPAGATE, DWELL_NAN_OMIT = 0, 1
+
+
+def gauss_dwell_evidence(model, ts, log_init, log_jump, log_dwell, log_surv, marginals=True, omit=False, scratch_bytes=0):
+    """
+    exact inference under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_evidence): a dict of logev,
+    map_logjoint (n_traj,), map_states (n_traj, T_max) uint8, n_nan_windows (n_traj,) int64 and, with marginals, log_post
+    (n_traj, S, T_max), exp_jumps (n_traj, S, S) and exp_stay (n_traj, S) (None without); T_max the set's longest trajectory
+    """
+    S = model.S
+    log_init, log_jump, log_dwell, log_surv = f64(log_init), f64(log_jump), f64(log_dwell), f64(log_surv)
+    L = log_dwell.shape[1]
+    assert log_init.shape == (S,) and log_jump.shape == (S, S) and log_dwell.shape == (S, L) and log_surv.shape == (S, L)
+    n = ts.n_traj
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty(n), 'map_logjoint': np.empty(n), 'map_states': np.empty((n, T_max), dtype=np.uint8),
+           'n_nan_windows': np.empty(n, dtype=np.int64),
+           'log_post': np.empty((n, S, T_max)) if marginals else None,
+           'exp_jumps': np.empty((n, S, S)) if marginals else None, 'exp_stay': np.empty((n, S)) if marginals else None}
+    spec = DwellOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
+    check(lib().bild_gauss_dwell_evidence(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
+                                          DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
     return res

@@ -103,3 +103,11 @@ int launch_segsens_weight(const SegdpParams &, const SegsensWeights &, void *) {
 int launch_segsens_solve(const GaussSensSet *, const SegsensJob *, int, int, int, const double *, double *, void *) { return 1; }
 int launch_segsens_factor(const GaussSensSet *, const SegsensJob *, int, int, const double *, double *, double *, void *) { return 1; }
 } // namespace bild
+#include "gauss_dwell.h"
+namespace bild {
+int launch_dwell_forward(const DwellParams &, void *) { return 1; }
+int launch_dwell_backward(const DwellParams &, void *) { return 1; }
+int launch_dwell_cover(const DwellParams &, void *) { return 1; }
+int launch_dwell_carry(const DwellParams &, void *) { return 1; }
+int launch_dwell_counts(const DwellParams &, void *) { return 1; }
+} // namespace bild

@@ -14,6 +14,10 @@ for every k up to k_max in one call.
 
 `exact_draw` (bild_gauss_segment_draw) draws profiles from that exact posterior, segment by segment
 against the recursion's backward tables: independent draws, without weights or burn-in.
+
+`exact_dwell` (bild_gauss_dwell_evidence) replaces the uniform prior per k by a dwell-time prior
+(`DwellPrior`): one evidence per trajectory over the profiles of every k, MAP profile, marginals and expected jump / stay
+counts; `fit_markov_prior` fits a Markov prior's switching rates to a data set by EM on those counts.
 """
 import math
 import warnings
@@ -525,3 +529,309 @@ def exact_sensitivities(trajs, model, dmsd=None, dmsd_inf=None, dmean=None, k_ma
                                            omit=nan == 'omit', fisher=fisher, scratch_bytes=scratch_bytes, **given)
     return EvidenceSensitivities(log_marginal=res['log_marginal'], k_posterior=res['k_post'], logev=res['logev'], grad=res['grad'],
                                  expected_logL=res['exp_logl'], fisher=res['fisher'])
+
+
+# ---------------------------------------------------------------- a dwell-time prior in place of the choice of k (section 21)
+
+MAX_S_DWELL = 4
+
+
+class DwellPrior:
+    """
+    An explicit-duration (semi-Markov) prior over looping profiles.  A profile of segments of lengths l_0 ... l_k in states
+    s_0 ... s_k has
+
+        log prior = log_init[s_0] + sum_{i<k} (log_dwell[s_i][l_i] + log_jump[s_i][s_{i+1}]) + log_surv[s_k][l_k]
+
+    (the last segment is right-censored; a single segment over the whole trajectory gets log_init + log_surv[.][T]).
+
+    log_init : (S,)
+    log_jump : (S, S), the diagonal -inf: a self-jump would split what the likelihood treats as one segment
+    log_dwell, log_surv : (S, L); column l - 1 is the entry of length l = 1 ... L, so the tables serve trajectories of up to L
+        frames, of every length
+
+    Entries are finite or -inf; `log_init` must not be -inf everywhere.  Anything else raises ValueError.  The tables need
+    not be normalised.  `DwellPrior.markov` gives the geometric tables of an ordinary Markov chain.
+    """
+
+    def __init__(self, log_init, log_jump, log_dwell, log_surv):
+        self.log_init = np.array(log_init, dtype=np.float64)
+        self.log_jump = np.array(log_jump, dtype=np.float64)
+        self.log_dwell = np.array(log_dwell, dtype=np.float64)
+        self.log_surv = np.array(log_surv, dtype=np.float64)
+        if self.log_init.ndim != 1 or len(self.log_init) < 1:
+            raise ValueError(f"log_init has shape {self.log_init.shape}; (S,) expected")
+        S = len(self.log_init)
+        if self.log_jump.shape != (S, S):
+            raise ValueError(f"log_jump has shape {self.log_jump.shape}; ({S}, {S}) expected")
+        if self.log_dwell.ndim != 2 or self.log_dwell.shape[0] != S or self.log_dwell.shape[1] < 1:
+            raise ValueError(f"log_dwell has shape {self.log_dwell.shape}; ({S}, L) with L >= 1 expected")
+        if self.log_surv.shape != self.log_dwell.shape:
+            raise ValueError(f"log_surv has shape {self.log_surv.shape}; that of log_dwell, {self.log_dwell.shape}, expected")
+        for name in ('log_init', 'log_jump', 'log_dwell', 'log_surv'):
+            a = getattr(self, name)
+            if np.any(np.isnan(a)) or np.any(a == np.inf):
+                raise ValueError(f"{name} has a NaN or +inf entry; entries must be finite or -inf")
+        if np.any(np.diag(self.log_jump) != -np.inf):
+            raise ValueError("the diagonal of log_jump must be -inf: a self-jump would split one segment into two")
+        if np.all(self.log_init == -np.inf):
+            raise ValueError("log_init is -inf everywhere")
+
+    @property
+    def nStates(self):
+        return len(self.log_init)
+
+    @property
+    def L(self):
+        """ the longest trajectory the tables serve """
+        return self.log_dwell.shape[1]
+
+    def __repr__(self):
+        return f"DwellPrior(S={self.nStates}, L={self.L})"
+
+    @classmethod
+    def markov(cls, P, init=None, n=2048):
+        """
+        The prior of a Markov chain with row-stochastic transition matrix P (S, S) and initial distribution init (uniform where
+        None), with tables for trajectories of up to n frames:
+
+            log_dwell[s][l] = (l - 1) log P_ss + log(1 - P_ss),  log_surv[s][l] = (l - 1) log P_ss,
+            log_jump[s][s'] = log(P_ss' / (1 - P_ss))
+
+        An absorbing state (P_ss = 1) never jumps: its log_jump row and log_dwell are -inf.
+        """
+        P = np.asarray(P, dtype=np.float64)
+        if P.ndim != 2 or P.shape[0] != P.shape[1]:
+            raise ValueError(f"P has shape {P.shape}; a square matrix expected")
+        S = len(P)
+        if not np.all(np.isfinite(P)) or np.any(P < 0) or np.any(np.abs(P.sum(axis=1) - 1) > 1e-9):
+            raise ValueError("P must be row-stochastic: finite, non-negative, rows summing to 1")
+        init = np.full(S, 1.0 / S) if init is None else np.asarray(init, dtype=np.float64)
+        if init.shape != (S,) or not np.all(np.isfinite(init)) or np.any(init < 0) or abs(init.sum() - 1) > 1e-9:
+            raise ValueError(f"init must be a distribution over the {S} states")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"n = {n!r}: a positive integer")
+        stay = np.diag(P).copy()
+        off = P - np.diag(stay)
+        leave = off.sum(axis=1)     # 1 - P_ss from the entries themselves: exact for small switching probabilities
+        lm1 = np.arange(n, dtype=np.float64)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            log_stay, log_leave = np.log(stay), np.log(leave)
+            surv = np.where(lm1[None, :] > 0, lm1[None, :] * log_stay[:, None], 0.0)      # (0 x -inf = 0: a segment of one frame)
+            log_jump = np.where(off > 0, np.log(off) - log_leave[:, None], -np.inf)
+            log_init = np.log(init)
+        return cls(log_init, log_jump, surv + log_leave[:, None], surv)
+
+    def log_prob(self, profile):
+        """ log prior of an expanded profile (a `Loopingprofile` or an integer array); host only """
+        states = np.asarray(profile[:], dtype=int)
+        T = len(states)
+        if T < 1 or T > self.L:
+            raise ValueError(f"profile of {T} frames: the tables serve 1 ... {self.L}")
+        if np.any(states < 0) or np.any(states >= self.nStates):
+            raise ValueError(f"profile has a state outside 0 ... {self.nStates - 1}")
+        cuts = np.concatenate(([0], np.flatnonzero(np.diff(states)) + 1, [T]))
+        total = self.log_init[states[0]]
+        for i in range(len(cuts) - 1):
+            s, length = states[cuts[i]], cuts[i + 1] - cuts[i]
+            if i + 2 < len(cuts):
+                total = total + self.log_dwell[s, length - 1] + self.log_jump[s, states[cuts[i + 1]]]
+            else:
+                total = total + self.log_surv[s, length - 1]
+        return float(total)
+
+
+class ExactDwellResults:
+    """
+    `exact_dwell` of one trajectory.
+
+    traj, model, prior, nan : as given
+    log_evidence : log sum over all profiles of prior x likelihood (NaN under nan='propagate' with `n_nan_windows` > 0)
+    map_profile : the profile of largest prior x likelihood as a `Loopingprofile` (None without a profile of finite prior weight
+        that uses no NaN window); map_log_joint : its log prior + log-likelihood (NaN without one)
+    log_marginal_posterior : (S, T) log P(theta_t = s | data), or None when not asked for
+    expected_jumps : (S, S) posterior expected number of jumps s -> s'; expected_stay : (S,) posterior expected number of frames
+        stayed in s (sum of length - 1 over its segments): the derivatives of `log_evidence` with respect to `log_jump` and to
+        a Markov chain's log P_ss.  None without marginals.
+    n_nan_windows : windows skipped because their table entry is NaN, among those of finite prior weight with a reachable start
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'log_evidence', 'map_profile', 'map_log_joint', 'log_marginal_posterior',
+                 'expected_jumps', 'expected_stay', 'n_nan_windows')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return (f"ExactDwellResults(T={len(self.traj)}, log_evidence={self.log_evidence!r}, map_log_joint={self.map_log_joint!r}, "
+                f"n_nan_windows={self.n_nan_windows})")
+
+
+def _check_exact_dwell(trajs, model, prior, nan):
+    """ every refusal of `exact_dwell`; returns (single, items) """
+    from .gauss import GenericGaussianModel
+    if not isinstance(model, GenericGaussianModel):
+        raise TypeError(f"exact_dwell needs a GenericGaussianModel, whose log-likelihood is a sum of segment terms, not "
+                        f"{type(model).__name__}")
+    if not isinstance(prior, DwellPrior):
+        raise TypeError(f"prior must be a DwellPrior, not {type(prior).__name__}")
+    if nan not in ('propagate', 'omit'):
+        raise ValueError(f"nan = {nan!r}: 'propagate' or 'omit'")
+    S = model.msd.shape[0]
+    if prior.nStates != S:
+        raise ValueError(f"the prior has {prior.nStates} states, the model {S}")
+    if S > MAX_S_DWELL:
+        raise ValueError(f"the model has {S} states: the dwell-time recursion supports at most {MAX_S_DWELL}")
+    single = not isinstance(trajs, (list, tuple))
+    items = [trajs] if single else list(trajs)
+    for t in items:
+        if len(t) > model.max_T:
+            raise ValueError(f"trajectory of {len(t)} frames: GenericGaussianModel evaluates at most {model.max_T} frames")
+        if len(t) > prior.L:
+            raise ValueError(f"trajectory of {len(t)} frames: the prior's tables serve at most {prior.L}")
+    return single, items
+
+
+def _dwell_results(items, model, prior, nan, res):
+    out = []
+    for j, t in enumerate(items):
+        T = len(t)
+        states = res['map_states'][j, :T]
+        profile = None if T == 0 or states[0] == 255 else Loopingprofile(states.astype(int))
+        marg = res['log_post'] is not None
+        out.append(ExactDwellResults(
+            traj=t, model=model, prior=prior, nan=nan, log_evidence=float(res['logev'][j]), map_profile=profile,
+            map_log_joint=float(res['map_logjoint'][j]), log_marginal_posterior=res['log_post'][j, :, :T].copy() if marg else None,
+            expected_jumps=res['exp_jumps'][j].copy() if marg else None, expected_stay=res['exp_stay'][j].copy() if marg else None,
+            n_nan_windows=int(res['n_nan_windows'][j])))
+    return out
+
+
+def exact_dwell(trajs, model, prior, marginals=True, nan='propagate', scratch_bytes=0):
+    """
+    Exact inference for a `GenericGaussianModel` under a dwell-time prior (`DwellPrior`) in place of "uniform over the profiles
+    of one k, k chosen by evidence": one evidence per trajectory over the profiles of every number of switches, the MAP
+    profile, the state marginals, and the expected jump and stay counts, by one forward and one backward recursion over
+    segments on the GPU (bild_gauss_dwell_evidence).
+
+    trajs : a trajectory or a list of them; a list gives a list of results from ONE device call
+    model : a `GenericGaussianModel` with at most 4 states (anything else: TypeError).  The prior's `log_jump` decides which
+        jumps exist; `model.transitions` is not consulted.
+    prior : a `DwellPrior` over the model's states whose tables cover the longest trajectory
+    marginals : compute `log_marginal_posterior`, `expected_jumps` and `expected_stay` (the backward pass)
+    nan : 'propagate' -- a trajectory with `n_nan_windows` > 0 (a later ss_order-0 segment without a valid frame that the prior
+        allows and a profile reaches) has NaN evidence, marginals and counts; its MAP profile is still taken among the
+        profiles that use no such window.  'omit' -- the profiles that use such a window weigh 0: the evidence is then that of
+        the prior RESTRICTED to the remaining profiles, not renormalised over them.
+    scratch_bytes : device workspace of one chunk of whole trajectories (0: at most 1 GiB and a third of the free memory)
+
+    MAP ties are broken as in `exact_sample`: the smallest final state, then from the last switch backwards the smallest
+    switch frame and the smallest preceding state.  Every refusal is raised before the trajectories are uploaded.  Returns
+    `ExactDwellResults` or a list of them.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    if not items:
+        return []
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_dwell_evidence(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
+                                    marginals=marginals, omit=nan == 'omit', scratch_bytes=scratch_bytes)
+    out = _dwell_results(items, model, prior, nan, res)
+    return out[0] if single else out
+
+
+class MarkovPriorFit:
+    """
+    `fit_markov_prior`'s result: P (S, S) and init (S,), the total log evidence of the data set at every iteration's
+    parameters (`log_evidence`, one entry per device call; the last belongs to the parameters one M-step before P),
+    n_iter and converged.  `prior(n)` is `DwellPrior.markov(P, init, n)`.
+    """
+
+    __slots__ = ('P', 'init', 'log_evidence', 'n_iter', 'converged')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return f"MarkovPriorFit(n_iter={self.n_iter}, converged={self.converged}, P={self.P!r})"
+
+    def prior(self, n=2048):
+        return DwellPrior.markov(self.P, self.init, n=n)
+
+
+def fit_markov_prior(trajs, model, start=None, tol=1e-8, max_iter=200, nan='propagate'):
+    """
+    Maximum-likelihood switching rates of a data set: EM over the transition matrix P and the initial distribution of a Markov
+    prior on the looping profiles, the model held fixed.  The trajectory set with its tables is built once; every iteration
+    is one `exact_dwell` device call on it, whose expected counts are the E-step:
+
+        P_ss' proportional to sum exp_jumps[s][s'],  P_ss proportional to sum exp_stay[s],  init_s = mean P(theta_0 = s)
+
+    trajs : a list of trajectories (or one)
+    model : a `GenericGaussianModel`; transitions that `model.transitions` forbids stay 0
+    start : None -- P_ss = 0.9, the rest spread evenly over the allowed transitions, uniform init; a matrix P; or (P, init)
+    tol : stop when an M-step moves no entry of P by more than this
+    max_iter : at most this many device calls
+    nan : as for `exact_dwell`; a NaN total evidence ('propagate' with NaN windows) raises ValueError
+
+    The total log evidence never decreases.  A state that the posterior never visits keeps its row.  Returns `MarkovPriorFit`.
+    """
+    from .gauss import GenericGaussianModel
+    if not isinstance(model, GenericGaussianModel):
+        raise TypeError(f"fit_markov_prior needs a GenericGaussianModel, whose log-likelihood is a sum of segment terms, not "
+                        f"{type(model).__name__}")
+    S = model.msd.shape[0]
+    allowed = np.asarray(model.transitions, dtype=bool).copy()
+    if allowed.shape != (S, S):
+        raise ValueError(f"model.transitions has shape {allowed.shape}; ({S}, {S}) expected")
+    np.fill_diagonal(allowed, False)
+    init = None
+    if start is None:
+        n_out = allowed.sum(axis=1)
+        P = np.where(allowed, 0.1 / np.maximum(n_out, 1)[:, None], 0.0)
+        P[np.arange(S), np.arange(S)] = 1.0 - P.sum(axis=1)
+    else:
+        if isinstance(start, tuple):
+            start, init = start
+        P = np.array(start, dtype=np.float64)
+        if P.shape != (S, S):
+            raise ValueError(f"start has shape {P.shape}; ({S}, {S}) expected")
+        if np.any((P > 0) & ~allowed & ~np.eye(S, dtype=bool)):
+            raise ValueError("start has a positive entry that model.transitions forbids")
+    init = np.full(S, 1.0 / S) if init is None else np.array(init, dtype=np.float64)
+    if not (tol > 0) or isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+        raise ValueError(f"tol = {tol!r} must be positive and max_iter = {max_iter!r} a positive integer")
+    single = not isinstance(trajs, (list, tuple))
+    items = [trajs] if single else list(trajs)
+    if not items:
+        raise ValueError("fit_markov_prior needs at least one trajectory")
+    n = max(len(t) for t in items)
+    _check_exact_dwell(items, model, DwellPrior.markov(P, init, n=n), nan)
+
+    ts = model.trajset(items[0] if single else items)       # built once: the iterations change the prior, not the tables
+    history, converged = [], False
+    for _ in range(int(max_iter)):
+        prior = DwellPrior.markov(P, init, n=n)
+        res = _lib.gauss_dwell_evidence(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
+                                        marginals=True, omit=nan == 'omit')
+        total = float(np.sum(res['logev']))
+        if not np.isfinite(total):
+            raise ValueError(f"the total log evidence is {total}: " + ("a trajectory has NaN windows, use nan='omit'"
+                                                                       if np.isnan(total) else "a trajectory has no profile of positive weight"))
+        history.append(total)
+        jumps, stay = res['exp_jumps'].sum(axis=0), res['exp_stay'].sum(axis=0)
+        jumps = np.where(allowed, jumps, 0.0)
+        denom = stay + jumps.sum(axis=1)
+        new = P.copy()
+        for s in range(S):
+            if denom[s] > 0:
+                new[s] = jumps[s] / denom[s]
+                new[s, s] = stay[s] / denom[s]
+        first = np.array([np.exp(res['log_post'][j, :, 0]) for j in range(len(items))]).mean(axis=0)
+        step = float(np.max(np.abs(new - P)))
+        P, init = new, first / first.sum()
+        if step < tol:
+            converged = True
+            break
+    return MarkovPriorFit(P=P, init=init, log_evidence=np.array(history), n_iter=len(history), converged=converged)

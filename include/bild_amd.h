@@ -962,6 +962,54 @@ int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const bild_gauss
                                      const uint8_t *transitions, unsigned flags, const double *log_k_prior, int P,
                                      const bild_gauss_derivs *dm, int64_t scratch_bytes, bild_segsens_out *out);
 
+/* ---------------------------------------------------------------- exact inference under a dwell-time prior ----
+ * GenericGaussianModel only, at most 4 states.  The profiles and the per-segment log-likelihood of
+ * the segment recursion above, under an explicit-duration (semi-Markov) prior in place of the uniform prior per k: a profile
+ * of segments [t_i, t_{i+1}) in states s_i, i = 0 .. k, t_0 = 0, t_{k+1} = T, lengths l_i = t_{i+1} - t_i >= 1, has
+ *   log prior = log_init[s_0] + sum_{i<k} (log_dwell[s_i][l_i] + log_jump[s_i][s_{i+1}]) + log_surv[s_k][l_k]
+ * (the last segment is right-censored; one segment over the whole trajectory gets log_init + log_surv[.][T]).  log_dwell and
+ * log_surv are S x L, the entry of length l = 1 .. L at column l - 1, and serve every trajectory of the set; the ordinary
+ * Markov chain is the geometric case.  Entries are finite or -inf.  There is one evidence per trajectory and no k:
+ *   logev          log sum over all profiles of exp(log prior + logL)
+ *   map_logjoint   the largest log prior + logL, and map_states a profile that attains it as T_max bytes of expanded states
+ *                  (255 behind T, and everywhere without a profile of finite prior weight; map_logjoint is then NaN).  Among
+ *                  equal maxima the smallest final state wins, then, from the last switch back, the smallest switch frame
+ *                  and then the smallest preceding state.
+ *   n_nan_windows  windows [a, b) in state s that were skipped because their table entry is NaN (DESIGN.md section 10,
+ *                  "Deviation"), counted where the prior weight of the segment is finite and a partial profile of finite
+ *                  prior weight without a NaN window reaches the start a in state s
+ *   log_post       S x T_max: log P(theta_t = s | data), NaN behind T; sums of non-negative terms only, not renormalised
+ *   exp_jumps      S x S: posterior expected number of jumps s' -> s
+ *   exp_stay       S: posterior expected number of frames stayed, sum over the segments in s of (length - 1)
+ * so that exp_jumps and exp_stay are the derivatives of logev with respect to log_jump and to the log of a Markov chain's
+ * P_ss.  log_post == NULL skips the backward and the statistics passes; exp_jumps and exp_stay are then not written.
+ * A NaN window never enters a maximum or a sum.  flags = 0 (BILD_DWELL_NAN_PROPAGATE): a trajectory with n_nan_windows > 0
+ * has NaN in logev, log_post, exp_jumps and exp_stay; its MAP profile is taken among the other profiles.
+ * BILD_DWELL_NAN_OMIT: the profiles that use such a window weigh 0, so logev is the evidence under the prior restricted to
+ * the remaining profiles (not renormalised).  The device does the same work in both modes.  A trajectory without a profile of
+ * positive weight has logev -inf and NaN in log_post, exp_jumps and exp_stay.  No atomics, fixed summation orders that depend
+ * on the trajectory alone: results are bit-identical across calls, the order of the set, a trajectory alone or in a batch, and
+ * scratch_bytes (chunks of whole trajectories; 0: at most 1 GiB and a third of the free device memory; at least one
+ * trajectory).  Refused before any device work: more than 4 states (BILD_ERR_UNSUPPORTED), L shorter than a trajectory of the
+ * set, a NaN or +inf table entry, a finite diagonal entry of log_jump (a self-jump would split what the likelihood treats as
+ * one segment), log_init that is -inf everywhere, unknown flags, a negative scratch_bytes, T_max shorter than a trajectory of
+ * the set (BILD_ERR_INVALID).  Plain launches on the set's stream.  Synchronous. */
+#define BILD_DWELL_NAN_PROPAGATE 0u
+#define BILD_DWELL_NAN_OMIT 1u
+
+typedef struct bild_dwell_out {
+    double *logev, *map_logjoint;           /* n_traj each */
+    uint8_t *map_states;                    /* n_traj x T_max */
+    int64_t *n_nan_windows;                 /* n_traj */
+    double *log_post;                       /* n_traj x S x T_max, NULL = forward pass only */
+    double *exp_jumps;                      /* n_traj x S x S */
+    double *exp_stay;                       /* n_traj x S */
+} bild_dwell_out;                           /* every pointer may be NULL: not written */
+
+int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
+                              const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, unsigned flags,
+                              int64_t scratch_bytes, bild_dwell_out *out);
+
 #ifdef __cplusplus
 }
 #endif
