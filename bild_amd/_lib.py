@@ -173,6 +173,9 @@ _SIGNATURES = {
     # exact inference under a dwell-time prior (gauss_dwell.cpp)
     'bild_gauss_dwell_evidence': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_uint, ctypes.c_int64,
                                                  _vp]),
+    # exact posterior draws under a dwell-time prior (gauss_dwelldraw.cpp)
+    'bild_gauss_dwell_draw': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _ip,
+                                             _vp, ctypes.c_int, _dp, ctypes.c_uint64, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1380,4 +1383,42 @@ def gauss_dwell_evidence(model, ts, log_init, log_jump, log_dwell, log_surv, mar
     spec = DwellOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
     check(lib().bild_gauss_dwell_evidence(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
                                           DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
+    return res
+
+
+class DwelldrawOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('states', 'n_switches', 'logl', 'log_prior', 'n_uniforms', 'uniforms_out')]
+
+
+def gauss_dwell_draw(model, ts, log_init, log_jump, log_dwell, log_surv, draw_traj, draw_stream=None, uniforms=None, keep_uniforms=0,
+                     seed=0, scratch_bytes=0):
+    """
+    exact posterior draws of profiles under a dwell-time prior (bild_gauss_dwell_draw): draw r on trajectory draw_traj[r] of
+    the set, from its row of ``uniforms`` (n, U) or, without them, from Philox stream draw_stream[r] (None: r) of ``seed``.  A
+    dict of states (n, T_max) uint8, n_switches, n_uniforms (n,) int32, logl, log_prior (n,) and uniforms (n, U): the first U
+    consumed, U = ``keep_uniforms`` in device mode (None where U = 0); T_max the set's longest trajectory
+    """
+    S = model.S
+    log_init, log_jump, log_dwell, log_surv = f64(log_init), f64(log_jump), f64(log_dwell), f64(log_surv)
+    L = log_dwell.shape[1]
+    assert log_init.shape == (S,) and log_jump.shape == (S, S) and log_dwell.shape == (S, L) and log_surv.shape == (S, L)
+    draw_traj = i32(draw_traj)
+    n, U = len(draw_traj), int(keep_uniforms)
+    assert draw_traj.shape == (n,)
+    if draw_stream is not None:
+        draw_stream = np.ascontiguousarray(draw_stream, dtype=np.int64)
+        assert draw_stream.shape == (n,)
+    if uniforms is not None:
+        uniforms = f64(uniforms)
+        assert uniforms.ndim == 2 and len(uniforms) == n
+        U = uniforms.shape[1]
+    T_max = int(np.max(ts.T))
+    res = {'states': np.empty((n, T_max), dtype=np.uint8), 'n_switches': np.empty(n, dtype=np.int32), 'logl': np.empty(n),
+           'log_prior': np.empty(n), 'n_uniforms': np.empty(n, dtype=np.int32), 'uniforms': np.zeros((n, U)) if U > 0 else None}
+    spec = DwelldrawOut(states=aptr(res['states']), n_switches=aptr(res['n_switches']), logl=aptr(res['logl']),
+                        log_prior=aptr(res['log_prior']), n_uniforms=aptr(res['n_uniforms']),
+                        uniforms_out=None if res['uniforms'] is None else aptr(res['uniforms']))
+    check(lib().bild_gauss_dwell_draw(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
+                                      int(scratch_bytes), n, iptr(draw_traj), None if draw_stream is None else aptr(draw_stream), U,
+                                      None if uniforms is None else aptr(uniforms), int(seed) & (2 ** 64 - 1), ctypes.byref(spec)))
     return res

@@ -111,3 +111,8 @@ int launch_dwell_cover(const DwellParams &, void *) { return 1; }
 int launch_dwell_carry(const DwellParams &, void *) { return 1; }
 int launch_dwell_counts(const DwellParams &, void *) { return 1; }
 } // namespace bild
+#include "gauss_dwelldraw.h"
+namespace bild {
+int launch_dwelldraw_head(const DwelldrawParams &, void *) { return 1; }
+int launch_dwelldraw(const DwelldrawParams &, const DwelldrawParams *, void *) { return 1; }
+} // namespace bild

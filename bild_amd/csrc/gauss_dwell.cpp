@@ -48,16 +48,11 @@ int check_logs(const char *name, const double *a, size_t n)
 
 } // namespace
 
-extern "C" int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
-                                         const double *log_jump, const double *log_dwell, const double *log_surv, int T_max,
-                                         unsigned flags, int64_t scratch_bytes, bild_dwell_out *out)
+namespace bild {
+
+int dwell_check_call(int S, int L, const double *log_init, const double *log_jump, const double *log_dwell, const double *log_surv,
+                     int n_traj, const int *T, int T_max, int64_t scratch_bytes)
 {
-    int n_traj = 0;
-    const int *T = nullptr;
-    DW_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
-    if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
-    if (flags & ~BILD_DWELL_NAN_OMIT) return fail(BILD_ERR_INVALID, "flags = %u: unknown bits", flags);
-    const int S = m->S;
     if (S > kDwellMaxS) return fail(BILD_ERR_UNSUPPORTED, "the model has %d states; the dwell-time recursion supports at most %d", S, kDwellMaxS);
     if (L < 1) return fail(BILD_ERR_INVALID, "L = %d: the dwell tables need at least one length", L);
     DW_TRY(check_logs("log_init", log_init, (size_t)S));
@@ -73,12 +68,28 @@ extern "C" int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_g
     }
     if (!any_init) return fail(BILD_ERR_INVALID, "log_init is -inf everywhere");
     if (scratch_bytes < 0) return fail(BILD_ERR_INVALID, "scratch_bytes = %lld is negative", (long long)scratch_bytes);
-    int Tm = 1;
     for (int j = 0; j < n_traj; ++j) {
         if (T[j] > T_max) return fail(BILD_ERR_INVALID, "trajectory %d has %d frames, more than T_max = %d", j, T[j], T_max);
         if (T[j] > L) return fail(BILD_ERR_INVALID, "trajectory %d has %d frames, more than the L = %d lengths of the dwell tables", j, T[j], L);
-        Tm = std::max(Tm, T[j]);
     }
+    return BILD_OK;
+}
+
+} // namespace bild
+
+extern "C" int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
+                                         const double *log_jump, const double *log_dwell, const double *log_surv, int T_max,
+                                         unsigned flags, int64_t scratch_bytes, bild_dwell_out *out)
+{
+    int n_traj = 0;
+    const int *T = nullptr;
+    DW_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
+    if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
+    if (flags & ~BILD_DWELL_NAN_OMIT) return fail(BILD_ERR_INVALID, "flags = %u: unknown bits", flags);
+    const int S = m->S;
+    DW_TRY(dwell_check_call(S, L, log_init, log_jump, log_dwell, log_surv, n_traj, T, T_max, scratch_bytes));
+    int Tm = 1;
+    for (int j = 0; j < n_traj; ++j) Tm = std::max(Tm, T[j]);
     if (n_traj == 0) return BILD_OK;
     const bool omit = (flags & BILD_DWELL_NAN_OMIT) != 0, marg = out->log_post != nullptr;
     const bool stats = marg;    // log_post == NULL: the forward pass alone

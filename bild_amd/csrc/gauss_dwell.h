@@ -43,6 +43,12 @@ struct DwellParams {
     int n_traj, S, L, Tm, ld, ntile;
 };
 
+// What every call on a dwell-time prior refuses about the prior and the set's lengths (gauss_dwell.cpp; host only): more than
+// kDwellMaxS states, L < 1 or shorter than a trajectory, a NaN or +inf table entry, a finite diagonal of log_jump, log_init
+// that is -inf everywhere, a negative scratch_bytes, T_max shorter than a trajectory.  A BILD_* code.
+int dwell_check_call(int S, int L, const double *log_init, const double *log_jump, const double *log_dwell, const double *log_surv,
+                     int n_traj, const int *T, int T_max, int64_t scratch_bytes);
+
 int launch_dwell_forward(const DwellParams &p, void *stream);
 int launch_dwell_backward(const DwellParams &p, void *stream);
 int launch_dwell_cover(const DwellParams &p, void *stream);

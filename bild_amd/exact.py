@@ -18,6 +18,9 @@ against the recursion's backward tables: independent draws, without weights or b
 `exact_dwell` (bild_gauss_dwell_evidence) replaces the uniform prior per k by a dwell-time prior
 (`DwellPrior`): one evidence per trajectory over the profiles of every k, MAP profile, marginals and expected jump / stay
 counts; `fit_markov_prior` fits a Markov prior's switching rates to a data set by EM on those counts.
+
+`exact_dwell_draw` (bild_gauss_dwell_draw) draws profiles from the exact posterior under that prior,
+segment by segment against the backward tables of the dwell-time recursion.
 """
 import math
 import warnings
@@ -26,7 +29,7 @@ import numpy as np
 from scipy.special import logsumexp
 
 from . import _lib
-from .profiles import Loopingprofile, states_from_segments
+from .profiles import Loopingprofile, segments_from_states, states_from_segments
 
 MAX_K = 15
 
@@ -667,6 +670,19 @@ class ExactDwellResults:
         return (f"ExactDwellResults(T={len(self.traj)}, log_evidence={self.log_evidence!r}, map_log_joint={self.map_log_joint!r}, "
                 f"n_nan_windows={self.n_nan_windows})")
 
+    def draw(self, n, seed=0, uniforms=None, keep_uniforms=0):
+        """ n profiles drawn from the exact posterior under the prior as `ExactDwellDraws`: `exact_dwell_draw` of these results """
+        return exact_dwell_draw(self, n, seed=seed, uniforms=uniforms, keep_uniforms=keep_uniforms)
+
+    def posterior_distance(self, n=1000, seed=0):
+        """
+        (mean, var), each (T, d): the smoothed track averaged over n profiles drawn from the exact posterior under the prior,
+        in one `model.kalman_mixture` call with equal weights -- the counterpart of `ExactSamplingResults.posterior_distance`
+        """
+        draws = exact_dwell_draw(self, n, seed=seed)
+        mean, var = self.model.kalman_mixture(draws.segments(), [self.traj], np.zeros(len(draws)))
+        return mean[0], var[0]
+
 
 def _check_exact_dwell(trajs, model, prior, nan):
     """ every refusal of `exact_dwell`; returns (single, items) """
@@ -737,6 +753,146 @@ def exact_dwell(trajs, model, prior, marginals=True, nan='propagate', scratch_by
     res = _lib.gauss_dwell_evidence(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
                                     marginals=marginals, omit=nan == 'omit', scratch_bytes=scratch_bytes)
     out = _dwell_results(items, model, prior, nan, res)
+    return out[0] if single else out
+
+
+# ---------------------------------------------------------------- profiles drawn under the dwell-time prior (section 22)
+
+class ExactDwellDraws:
+    """
+    Profiles of one trajectory drawn independently from the exact posterior under a dwell-time prior (`exact_dwell_draw`).
+
+    T : frames of the trajectory
+    n_switches : (n,) switches of each draw
+    logL, log_prior : (n,) log-likelihood and log prior of each drawn profile, from the tables the draw was made on
+    n_uniforms : (n,) uniforms each draw consumed, 1 + 2 `n_switches`
+    uniforms : (n, U) the first U uniforms each draw consumed (0 where none was), U = ``keep_uniforms`` or the width of the
+        replayed rows; None when neither was given.  Given back as ``uniforms=`` they reproduce the draws.
+    """
+
+    def __init__(self, T, states, n_switches, logL, log_prior, n_uniforms, uniforms):
+        self.T = int(T)
+        self._states = np.asarray(states, dtype=np.uint8)
+        self.n_switches = np.asarray(n_switches, dtype=np.int64)
+        self.logL = np.asarray(logL, dtype=np.float64)
+        self.log_prior = np.asarray(log_prior, dtype=np.float64)
+        self.n_uniforms = np.asarray(n_uniforms, dtype=np.int64)
+        self.uniforms = None if uniforms is None else np.asarray(uniforms, dtype=np.float64)
+
+    def __len__(self):
+        return len(self.n_switches)
+
+    def __repr__(self):
+        return f"ExactDwellDraws(n={len(self)}, T={self.T}, n_switches={np.unique(self.n_switches).tolist()})"
+
+    def states(self):
+        """ (n, T) int array: the state of every frame of every draw """
+        return self._states[:, :self.T].astype(int)
+
+    def profiles(self):
+        """ the draws as a list of `Loopingprofile` """
+        return [Loopingprofile(row) for row in self.states()]
+
+    def segments(self):
+        """ (seg_start, seg_state), each (n, max switches + 1) int32: run-length rows padded with empty segments at T """
+        if len(self) == 0:
+            return np.zeros((0, 1), dtype=np.int32), np.zeros((0, 1), dtype=np.int32)
+        return segments_from_states(self.states())
+
+    def dwell_lengths(self, state, completed=True):
+        """
+        the lengths of the drawn segments in ``state``, concatenated over the draws; ``completed`` leaves out each draw's
+        last segment, which the end of the trajectory censors (host only)
+        """
+        st = self._states[:, :self.T]
+        n, T = st.shape
+        if n == 0 or T == 0:
+            return np.zeros(0, dtype=np.int64)
+        first = np.ones((n, T), dtype=bool)
+        first[:, 1:] = st[:, 1:] != st[:, :-1]
+        rows, starts = np.nonzero(first)
+        last = np.append(rows[1:] != rows[:-1], True)       # the segment is its draw's last
+        ends = np.where(last, T, np.append(starts[1:], T))
+        use = st[rows, starts] == state
+        if completed:
+            use &= ~last
+        return (ends - starts)[use].astype(np.int64)
+
+
+def exact_dwell_draw(results, n, seed=0, uniforms=None, keep_uniforms=0, scratch_bytes=0):
+    """
+    n profiles per trajectory, drawn independently from the exact posterior under the dwell-time prior of `exact_dwell`, by
+    sampling segment after segment against the backward tables of the dwell-time recursion on the GPU (DESIGN.md section
+    22): no burn-in, no weights, no k and no k_max.
+
+    results : an `ExactDwellResults` or a list of them over one model and one prior; a list is served by ONE device call on
+        one trajectory set and gives a list of `ExactDwellDraws`
+    n : draws per result
+    seed : of the device's uniforms; draw i of result j is stream j n + i
+    uniforms : replay -- (n, U) uniforms in [0, 1), for a list of results (len(results), n, U), U >= 1: rows of
+        `ExactDwellDraws.uniforms` of an earlier call; ``seed`` is then not used.  A draw of k switches consumes 1 + 2k of
+        its row; a row that is too short raises ValueError (U = 2T - 1 always suffices).
+    keep_uniforms : device mode -- return the first ``keep_uniforms`` uniforms each draw consumed
+    scratch_bytes : device workspace of one chunk of whole trajectories (0: at most 1 GiB and a third of the free memory)
+
+    Profiles that use a NaN window are never drawn: results made with nan='omit' give draws from the posterior without
+    them; results made with nan='propagate' that have `n_nan_windows` > 0, and results whose `log_evidence` is -inf, raise
+    ValueError.  Every refusal but the short replay row is raised before any upload.  Returns an `ExactDwellDraws` or a
+    list of them.
+    """
+    single = isinstance(results, ExactDwellResults)
+    if not single and not isinstance(results, (list, tuple)):
+        raise TypeError(f"exact_dwell_draw needs ExactDwellResults (from exact_dwell) or a list of them, not {type(results).__name__}")
+    items = [results] if single else list(results)
+    if any(not isinstance(r, ExactDwellResults) for r in items):
+        raise TypeError("exact_dwell_draw needs ExactDwellResults (from exact_dwell) or a list of them")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError(f"n = {n!r}: a non-negative integer")
+    if isinstance(keep_uniforms, bool) or not isinstance(keep_uniforms, (int, np.integer)) or keep_uniforms < 0:
+        raise ValueError(f"keep_uniforms = {keep_uniforms!r}: a non-negative integer")
+    n = int(n)
+    if not items:
+        return []
+    model, prior = items[0].model, items[0].prior
+    if any(r.model is not model for r in items):
+        raise ValueError("exact_dwell_draw needs results over one model")
+    if any(r.prior is not prior for r in items):
+        raise ValueError("exact_dwell_draw needs results under one prior")
+    for j, r in enumerate(items):
+        if r.nan == 'propagate' and r.n_nan_windows > 0:
+            raise ValueError(f"result {j} was made with nan='propagate' and has {r.n_nan_windows} NaN windows: make the results "
+                             f"with nan='omit', which leaves the profiles that use them out")
+        if r.log_evidence == -np.inf:
+            raise ValueError(f"the log evidence of result {j} is -inf: no profile of positive weight to draw")
+    U = int(keep_uniforms)
+    if uniforms is not None:
+        uniforms = np.asarray(uniforms, dtype=np.float64)
+        if uniforms.ndim != (2 if single else 3) or uniforms.shape[:-1] != ((n,) if single else (len(items), n)) or uniforms.shape[-1] < 1:
+            want = f"({n}, U)" if single else f"({len(items)}, {n}, U)"
+            raise ValueError(f"uniforms has shape {uniforms.shape}; {want} with U >= 1 expected")
+        if not np.all((uniforms >= 0) & (uniforms < 1)):
+            raise ValueError("uniforms must lie in [0, 1) (NaN or a value outside given)")
+        U = uniforms.shape[-1]
+        uniforms = uniforms.reshape(len(items) * n, U)
+    if n == 0:
+        out = [ExactDwellDraws(len(r.traj), np.zeros((0, len(r.traj)), dtype=np.uint8), np.zeros(0), np.zeros(0), np.zeros(0),
+                               np.zeros(0), np.zeros((0, U)) if U else None) for r in items]
+        return out[0] if single else out
+    ts = model.trajset(items[0].traj if single else [r.traj for r in items])
+    res = _lib.gauss_dwell_draw(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
+                                np.repeat(np.arange(len(items)), n), uniforms=uniforms, keep_uniforms=U, seed=seed,
+                                scratch_bytes=scratch_bytes)
+    short = np.flatnonzero(res['n_uniforms'] < 0)
+    if len(short):
+        j, i = divmod(int(short[0]), n)
+        T = len(items[j].traj)
+        raise ValueError(f"draw {i}" + ("" if single else f" of result {j}") + f" needs more than the {U} uniforms of its row: "
+                         f"rows of 2T - 1 = {2 * T - 1} uniforms always suffice")
+    out = []
+    for j, r in enumerate(items):
+        rows = slice(j * n, (j + 1) * n)
+        out.append(ExactDwellDraws(len(r.traj), res['states'][rows], res['n_switches'][rows], res['logl'][rows], res['log_prior'][rows],
+                                   res['n_uniforms'][rows], None if res['uniforms'] is None else res['uniforms'][rows]))
     return out[0] if single else out
 
 

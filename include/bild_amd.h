@@ -1010,6 +1010,55 @@ int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_gauss_trajse
                               const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, unsigned flags,
                               int64_t scratch_bytes, bild_dwell_out *out);
 
+/* ---------------------------------------------------------------- exact posterior draws under a dwell-time prior ----
+ * GenericGaussianModel only, at most 4 states.  Independent draws from the exact posterior over the
+ * profiles of every number of switches under the dwell-time prior of the block above (same tables, same refusals), by
+ * sampling a profile segment by segment from the left against the backward tables of that recursion: beta(a, s) =
+ * log sum_{b > a} exp(omega_s(a, b) + W[s][a - 1][b] + gamma(b, s)), gamma(b, s) = log sum_q exp(log_jump[s][q] + beta(b, q))
+ * for b < T and 0 for b = T, with omega_s(a, b) = log_dwell[s][b - a] for b < T and log_surv[s][T - a] for b = T.  There is
+ * no k and no k_max.  Draw r belongs to trajectory draw_traj[r] of the set and consumes uniforms u[0], u[1], .. in [0, 1):
+ *   u[0]       (s_0, t_1) jointly, the list ordered by state, then by the end frame b = 1 .. T, log weights
+ *              log_init[s] + omega_s(0, b) + F[s][b] + gamma(b, s); t_1 = T ends the draw with 0 switches
+ *   u[2i - 1]  s_i among q = 0 .. S - 1, ascending, log weights log_jump[s_{i-1}][q] + beta(t_i, q); the list's total is
+ *              gamma(t_i, s_{i-1})
+ *   u[2i]      t_{i+1} among b = t_i + 1 .. T, ascending, log weights omega_{s_i}(t_i, b) + W[s_i][t_i - 1][b] + gamma(b, s_i);
+ *              the list's total is beta(t_i, s_i).  The draw ends when a pick returns b = T,
+ * for i = 1, 2, ..: a draw of k switches consumes exactly 1 + 2k uniforms (at most 2T - 1).  A pick returns the first entry
+ * of positive weight whose inclusive running weight exceeds u times the list's total, and the last entry of positive
+ * weight where rounding carries that product past the end; an entry of weight 0 -- a NaN window (DESIGN.md section 10,
+ * "Deviation"), a prior term of -inf, gamma = -inf behind an absorbing state -- is never returned, so a NaN profile is never
+ * drawn.  A pick with one candidate still consumes its uniform.  Per draw:
+ *   states        T_max bytes: the expanded profile, 255 behind T (the layout of bild_dwell_out.map_states)
+ *   n_switches    k
+ *   logl          F[s_0][t_1] + sum_i W[s_i][t_i - 1][t_{i+1}], added from the left onto 0.0 as bild_gauss_logl_segments adds it
+ *   log_prior     log_init[s_0], then per completed segment + log_dwell, + log_jump, at last + log_surv, in that order
+ *   n_uniforms    the uniforms consumed
+ *   uniforms_out  the first U uniforms consumed, 0 where none was
+ * A trajectory without a profile of positive weight gives a row of 255, n_switches -1, NaN in logl and log_prior and
+ * n_uniforms 0.  Device mode, uniforms == NULL: draw r takes its uniforms on demand, without limit, from the
+ * Philox-4x32-10 stream (key: seed; counter: draw_stream[r], or r where draw_stream is NULL) in the order above, so a draw
+ * is a pure function of (seed, its stream index, its trajectory's tables, the prior).  Replay, uniforms given (n_draws x
+ * U): seed is ignored; a draw that needs more than U uniforms is not completed and gets the 255 row, n_switches -1, NaN
+ * and n_uniforms -1 (U = 2 T_max - 1 always suffices).  U may be 0 in device mode: nothing is kept.  Results do not depend on
+ * the other draws, on the set's other trajectories or their order, or on scratch_bytes (chunks of whole trajectories as in
+ * bild_gauss_dwell_evidence, 16 S (T + 1) bytes each for beta and gamma, T the longest trajectory a draw names; trajectories
+ * that no draw names are skipped; the forward tables are not built).  Refused before any device work: what
+ * bild_gauss_dwell_evidence refuses, n_draws < 0, a draw_traj out of range, U < 0, a replay with U < 1, a uniform outside
+ * [0, 1) or NaN (BILD_ERR_INVALID).  n_draws = 0 returns at once.  Plain launches on the set's stream, no atomics.
+ * Synchronous. */
+typedef struct bild_dwelldraw_out {
+    uint8_t *states;                        /* n_draws x T_max */
+    int32_t *n_switches;                    /* n_draws */
+    double *logl, *log_prior;               /* n_draws each */
+    int32_t *n_uniforms;                    /* n_draws */
+    double *uniforms_out;                   /* n_draws x U */
+} bild_dwelldraw_out;                       /* every pointer may be NULL: not written */
+
+int bild_gauss_dwell_draw(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
+                          const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, int64_t scratch_bytes,
+                          int64_t n_draws, const int32_t *draw_traj, const int64_t *draw_stream, int U, const double *uniforms,
+                          uint64_t seed, bild_dwelldraw_out *out);
+
 #ifdef __cplusplus
 }
 #endif
