@@ -15,7 +15,8 @@ import segment_cases as C
 
 N_REPLAY = 4096
 
-# name: (S, T, missing frames, prior kind, seed of the uniforms)
+# name: (S, T, missing frames, prior kind of `dwell_cases.prior_of`, seed of the uniforms[, draws: the first rows of the
+# (N_REPLAY, 2T - 1) uniforms of that seed, where the oracle would take a minute for all of them])
 REPLAY_CASES = {
     's2_T1_markov': (2, 1, (), 'markov', 1),
     's2_T2_minlength': (2, 2, (), 'minlength', 2),
@@ -29,13 +30,20 @@ REPLAY_CASES = {
     's3_T193_markov': (3, 193, (), 'markov', 10),
     's3_T65_absorbing': (3, 65, (20,), 'absorbing', 11),
     's2_T70_order0_gap': (2, 70, (), 'markov', 12),
+    # S = 1 and S = 4, non-geometric and length-bounded tables, and more than 256 frames
+    's1_T65_markov': (1, 65, (), 'markov', 21),
+    's4_T65_nongeometric': (4, 65, (7,), 'nongeometric', 22),
+    's4_T130_minlength': (4, 130, (64,), 'minlength', 23),
+    's2_T257_markov': (2, 257, (255,), 'markov', 24, 1024),
+    's3_T321_nongeometric': (3, 321, (128,), 'nongeometric', 25, 1024),
+    's2_T130_bounded': (2, 130, (), 'bounded', 26),
 }
 
 
-def absorbing_prior(rng, L):
-    """ three states, 0 -> 2 forbidden, state 2 absorbing: its jumps and dwells are -inf, gamma behind it is -inf before T """
-    P = np.array([[0.85, 0.15, 0.0], [0.1, 0.8, 0.1], [0.0, 0.0, 1.0]])
-    return bild_amd.DwellPrior.markov(P, rng.dirichlet(np.ones(3)), n=L)
+def n_replay(name):
+    """ the draws of a case """
+    case = REPLAY_CASES[name]
+    return case[5] if len(case) > 5 else N_REPLAY
 
 
 def order0_gap_case(rng, T):
@@ -48,16 +56,34 @@ def order0_gap_case(rng, T):
 
 
 def replay_case(name):
-    """ (model, x, prior, uniforms (N_REPLAY, 2T - 1)) """
-    S, T, missing, kind, seed = REPLAY_CASES[name]
+    """ (model, x, prior, uniforms (n_replay(name), 2T - 1)) """
+    S, T, missing, kind, seed = REPLAY_CASES[name][:5]
     rng = np.random.default_rng(1000 * S + T)
     if 'order0' in name:
         model, x = order0_gap_case(rng, T)
     else:
         model = C.random_model(rng, S, T + 8)
         x = C.random_traj(rng, T, missing)
-    prior = absorbing_prior(rng, T + 5) if kind == 'absorbing' else DC.make_prior(kind, rng, S, T + 5)
-    return model, x, prior, np.random.default_rng(seed).random((N_REPLAY, 2 * T - 1))
+    prior = DC.prior_of(kind, rng, S, T + 5, T)
+    return model, x, prior, np.random.default_rng(seed).random((N_REPLAY, 2 * T - 1))[:n_replay(name)]
+
+
+N_SIX = 200     # draws per trajectory of the six-trajectory call
+
+
+def six_uniforms():
+    """ the replayed uniforms (6, N_SIX, 2 * 257 - 1) of the call that draws on `dwell_cases.ragged_case`'s six trajectories """
+    return np.random.default_rng(27).random((len(DC.RAGGED), N_SIX, 2 * 257 - 1))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_six(j):
+    """ `dwell_draw_oracle.draws` of trajectory j of the six, arrays read-only """
+    _, prior, _, tabs = DC.ragged_case()
+    out = DDO.draws(*tabs[j], prior, six_uniforms()[j])
+    for a in out.values():
+        a.setflags(write=False)
+    return out
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,7 +1,8 @@
 """
 The dwell-time recursion without a GPU (bild_amd.exact.exact_dwell): the NumPy oracle
 tests/dwell_oracle.py against the enumeration of every profile of every k, its identities, the symmetric two-state chain
-against the segment recursion's oracle, `DwellPrior`, and the refusals.
+against the segment recursion's oracle, `DwellPrior`, the refusals, and the conditions on the inputs of the GPU test's oracle
+cases (`dwell_cases.ORACLE_CASES`, the ragged batch and the sharp case), whose oracle answers are computed here as there.
 """
 import numpy as np
 import pytest
@@ -193,3 +194,88 @@ def test_refusals_come_before_any_upload(monkeypatch):
     with pytest.raises(ValueError):         # a start that uses the forbidden transition 0 -> 2
         bild_amd.fit_markov_prior([x], three, start=np.full((3, 3), 1 / 3))
     assert bild_amd.exact_dwell([], model, prior) == []
+
+
+def test_hard_priors():
+    rng = np.random.default_rng(8)
+    T = 150
+    prior = DC.prior_of('bounded', rng, 2, T + 5, T)
+    assert DC.BOUND == 70 and np.all(np.isfinite(prior.log_dwell[:, :70])) and np.all(prior.log_surv[:, 70:] == -np.inf)
+    st = np.zeros(T, dtype=int)
+    st[10:80] = 1       # 70 frames, completed; the first and the last segment have 10 and 70
+    assert np.isfinite(prior.log_prob(st))
+    st[80] = 1          # 71
+    assert prior.log_prob(st) == -np.inf
+    st = np.repeat([1, 0, 1], [40, 39, 71])     # a censored last segment of 71 frames
+    assert len(st) == T and prior.log_prob(st) == -np.inf
+    assert np.isfinite(prior.log_prob(np.repeat([1, 0, 1], [40, 40, 70])))
+    for kind in ('markov', 'minlength', 'nongeometric'):    # passed through unchanged, the same numbers drawn
+        a, b = DC.prior_of(kind, np.random.default_rng(9), 3, 20, 15), DC.make_prior(kind, np.random.default_rng(9), 3, 20)
+        assert all(np.array_equal(getattr(a, n), getattr(b, n)) for n in ('log_init', 'log_jump', 'log_dwell', 'log_surv'))
+    one = DC.prior_of('one_start', rng, 3, 20, 15)
+    assert one.log_init.tolist() == [-np.inf, -np.inf, 0.0] and one.log_prob([0, 0, 1]) == -np.inf and np.isfinite(one.log_prob([2, 1, 1]))
+    flip = DC.prior_of('flip', rng, 2, 20, 15)
+    assert abs(flip.log_prob([1, 0, 1, 0]) - np.log(0.7)) < 1e-15 and flip.log_prob([1, 1, 0, 1]) == -np.inf
+    no = DC.prior_of('impossible', rng, 2, 10, 6)
+    assert all(no.log_prob(row) == -np.inf for _, _, _, states in DO.all_profiles(6, 2) for row in states)
+    assert np.isfinite(no.log_prob(np.zeros(5, dtype=int)))       # (a shorter trajectory has the profile of one segment)
+    assert np.all(DC.prior_of('absorbing', rng, 3, 20, 15).log_jump[2] == -np.inf)
+
+
+@pytest.mark.parametrize('S,T,missing,kind', DC.ORACLE_CASES[DC.N_ORACLE_CASES_BEFORE:])
+def test_gpu_oracle_cases_meet_their_conditions(S, T, missing, kind):
+    """ conditions on the GPU test's inputs: what tests/test_gpu_dwell.py compares the device with is what it is meant to be """
+    case = (S, T, missing, kind)
+    model, x, prior, W, F = DC.oracle_case(case)
+    assert model.nStates == prior.nStates == S and x.shape == (T, 2) and prior.L == T + 5
+    assert np.array_equal(np.flatnonzero(np.isnan(x[:, 0])), missing)
+    want = DC.oracle_answer(case)
+    print(f"{case}: oracle {DC.ORACLE_SECONDS[case]:.1f} s, logev {want['logev']}")
+    assert DC.ORACLE_SECONDS[case] < 20
+    assert want['n_nan_windows'] == 0
+    post = want['log_post']
+    if kind == 'impossible':
+        assert want['logev'] == -np.inf and want['map_states'] is None and np.isnan(want['map_logjoint'])
+        assert np.all(np.isnan(post)) and np.all(np.isnan(want['exp_jumps'])) and np.all(np.isnan(want['exp_stay']))
+        return
+    assert np.isfinite(want['logev']) and np.isfinite(want['map_logjoint']) and want['map_states'] is not None
+    assert not np.any(np.isnan(post)) and np.all(np.isfinite(want['exp_jumps'])) and np.all(np.isfinite(want['exp_stay']))
+    assert np.max(np.abs(np.exp(post).sum(axis=0) - 1)) < 1e-9
+    if kind == 'one_start':
+        assert np.all(post[:S - 1, 0] == -np.inf) and abs(post[S - 1, 0]) < 1e-12 and 0.99 < np.mean(np.isfinite(post)) < 1
+    else:
+        assert np.all(np.isfinite(post))
+    if kind == 'bounded':       # every tile seam is crossed by a switch
+        runs = np.diff(np.concatenate(([0], np.flatnonzero(np.diff(want['map_states'])) + 1, [T])))
+        assert runs.max() <= DC.BOUND and len(runs) >= T / DC.BOUND
+    if kind == 'flip':
+        assert np.all(np.diff(want['map_states']) != 0) and abs(want['exp_jumps'].sum() - (T - 1)) < 1e-9
+    if kind == 'absorbing':
+        assert np.all(want['exp_jumps'][2] == 0) and want['exp_jumps'][0, 2] == 0
+    if S == 1:
+        assert np.all(post == 0) and np.array_equal(want['exp_jumps'], [[0.0]]) and want['exp_stay'][0] == T - 1
+
+
+def test_gpu_ragged_batch_meets_its_conditions():
+    model, prior, xs, tabs = DC.ragged_case()
+    assert [len(x) for x in xs] == [T for T, _ in DC.RAGGED] and model.nStates == 4 and prior.L == 262
+    for j, want in enumerate(DC.ragged_answers()):
+        print(f"trajectory {j}: oracle {DC.ORACLE_SECONDS['ragged', j]:.1f} s, logev {want['logev']}")
+        assert DC.ORACLE_SECONDS['ragged', j] < 20
+        assert want['n_nan_windows'] == 0 and np.isfinite(want['logev']) and np.isfinite(want['map_logjoint'])
+        assert np.all(np.isfinite(want['log_post'])) and np.all(np.isfinite(want['exp_jumps'])) and np.all(np.isfinite(want['exp_stay']))
+
+
+def test_gpu_sharp_case_meets_its_conditions():
+    model, x, prior, st, W, F = DC.sharp_case()
+    want = DC.sharp_answer()
+    post = want['log_post']
+    low = post < -600       # (-inf among them)
+    print(f"sharp: oracle {DC.ORACLE_SECONDS['sharp']:.1f} s, logev {want['logev']}, min finite W {np.min(W[np.isfinite(W)]):.4g}, "
+          f"finite log_post {np.mean(np.isfinite(post)):.3f}, below -600: {int(low.sum())}, -inf: {int(np.sum(post == -np.inf))}, lowest finite {np.min(post[np.isfinite(post)]):.1f}")
+    assert DC.ORACLE_SECONDS['sharp'] < 20
+    assert want['n_nan_windows'] == 0 and abs(want['logev'] + 207.416) < 1e-3
+    assert np.array_equal(want['map_states'], st)
+    assert -1.2e5 < np.min(W[np.isfinite(W)]) < -1.0e5
+    assert not np.any(np.isnan(post)) and 0.8 < np.mean(np.isfinite(post)) < 0.95
+    assert 20 <= low.sum() <= 60

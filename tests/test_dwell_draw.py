@@ -84,7 +84,7 @@ def test_absorbing_state_and_minimum_length():
     model = C.random_model(rng, 3, T + 4)
     x = C.random_traj(rng, T, (4,))
     W, F = C.tables(model, x)
-    prior = DDC.absorbing_prior(rng, T)
+    prior = DC.absorbing_prior(rng, T)
     B, G = DDO.backward(W, F, prior)
     assert np.all(G[1:T, 2] == -np.inf) and G[T, 2] == 0 and np.all(np.isfinite(G[1:T, :2]))
     d = DDO.draws(W, F, prior, rng.random((5000, 2 * T - 1)))
@@ -206,9 +206,22 @@ def test_refusals_come_before_any_upload(monkeypatch):
 def test_gpu_replay_inputs_are_not_fragile(name):
     """ a condition on the GPU test's inputs: the oracle alone flags none of their draws (expectation ~2 DELTA per pick) """
     want = DDC.oracle_replay(name)
-    T = DDC.REPLAY_CASES[name][1]
+    S, T = DDC.REPLAY_CASES[name][:2]
+    n = DDC.n_replay(name)
+    assert n in (1024, DDC.N_REPLAY)
     assert not want['fragile'].any()
     assert np.all(want['n_switches'] >= 0) and np.array_equal(want['n_uniforms'], 1 + 2 * want['n_switches'])
-    assert want['states'].shape == (DDC.N_REPLAY, T) and np.all(want['states'] < DDC.REPLAY_CASES[name][0])
-    if T > 3:
-        assert len(np.unique(want['states'], axis=0)) > DDC.N_REPLAY // 20
+    assert want['states'].shape == (n, T) and np.all(want['states'] < S)
+    if S == 1:
+        assert np.all(want['n_switches'] == 0) and np.all(want['states'] == 0)     # one profile, one uniform a draw
+    elif T > 3:
+        assert len(np.unique(want['states'], axis=0)) > n // 20
+
+
+@pytest.mark.parametrize('j', [1, 5])
+def test_gpu_six_trajectory_inputs(j):
+    """ a condition on the GPU test's inputs: the oracle excuses at most one of a trajectory's draws """
+    want = DDC.oracle_six(j)
+    T = DC.RAGGED[j][0]
+    assert want['states'].shape == (DDC.N_SIX, T) and np.all(want['states'] < 4) and want['fragile'].sum() <= 1
+    assert np.all(want['n_switches'] >= 0) and len(np.unique(want['states'], axis=0)) > DDC.N_SIX // 20

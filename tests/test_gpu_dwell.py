@@ -1,10 +1,18 @@
 """
 The dwell-time recursion on the GPU (bild_amd.exact.exact_dwell, csrc/gauss_dwell.hip): against the
-NumPy oracle tests/dwell_oracle.py around the 64-frame tiles, against `exact_sample` through the symmetric two-state chain,
-Fisher's identity for the expected counts, T = 1000, bit-identity across calls, batch orders, batch sizes and chunking, and
-the EM fit of a Markov prior.  Tolerances as in tests/test_gpu_segment_dp.py: logev, finite log marginals and the MAP log
-joint 1e-10, counts 1e-9 relative.  Worst seen on the MI355X: logev 1.1e-13, log marginals 1.6e-13, MAP log joint 3.4e-13, counts
+NumPy oracle tests/dwell_oracle.py around the 64-frame tiles, at one to four states, beyond the 256 frames of the statistics
+kernels' first workgroup and under the priors of `dwell_cases.prior_of` (`dwell_cases.ORACLE_CASES`), a ragged batch of six
+against the oracle, a sharp posterior, against `exact_sample` through the symmetric two-state chain, Fisher's identity for
+the expected counts, T = 1000, bit-identity across calls, batch orders, batch sizes and chunking, and the EM fit of a Markov
+prior.  Tolerances as in tests/test_gpu_segment_dp.py: logev, finite log marginals and the MAP log joint 1e-10, counts 1e-9
+relative.  Worst seen on the MI355X: logev 1.1e-13, log marginals 1.6e-13, MAP log joint 3.4e-13, counts
 5.0e-12 absolute; Fisher quotients within 2.5e-9 of the counts; `-s` prints every figure.
+With the cases at S = 1 and 4, T > 256 and the hard priors, worst seen on the MI355X: logev 9.7e-13 (S = 1, T = 130, non-geometric:
+one profile, the evidence is its log joint), log marginals 6.4e-12 (the absorbing prior; 9.7e-13 elsewhere), MAP log joint
+2.3e-11 (S = 3, T = 321, frame 128 missing; 1.0e-12 elsewhere), counts 3.8e-11 absolute (an expected stay at T = 321).
+The ragged batch: logev 2.3e-13, log marginals 4.8e-13, MAP log joint 6.8e-13, counts 1.4e-11 absolute.  The sharp case (its bar
+3.7e-9): logev 2.8e-14, MAP log joint 2.8e-14, the 224 log marginals at or above -600 1.1e-13, counts 1.9e-12 absolute; of the 36
+entries whose reference is below -600, the device has -inf on the 34 where the oracle has, and at most -707.48 on the other two.
 """
 import ctypes
 
@@ -39,11 +47,13 @@ def check_against_oracle(r, want, W, F, prior, exact_map):
         print('log_post', np.max(np.abs(got[fin] - ref[fin])))
         assert np.max(np.abs(got[fin] - ref[fin])) < 1e-10
     for name, got, ref in (('jumps', r.expected_jumps, want['exp_jumps']), ('stay', r.expected_stay, want['exp_stay'])):
-        if np.all(np.isnan(ref)):
-            assert np.all(np.isnan(got)), name
-            continue
-        print(name, np.max(np.abs(got - ref)))
-        assert np.all(np.abs(got - ref) <= 1e-9 * np.abs(ref)), (name, got, ref)
+        assert got.shape == ref.shape
+        fin = np.isfinite(ref)
+        # (a reference that is not finite: the same value at the same place)
+        assert np.array_equal(got[~fin], ref[~fin], equal_nan=True), (name, got, ref)
+        if fin.any():
+            print(name, np.max(np.abs(got[fin] - ref[fin])))
+            assert np.all(np.abs(got[fin] - ref[fin]) <= 1e-9 * np.abs(ref[fin])), (name, got, ref)
     if want['map_states'] is None:
         assert r.map_profile is None
         return
@@ -54,24 +64,78 @@ def check_against_oracle(r, want, W, F, prior, exact_map):
     assert abs(prior.log_prob(states) + G.logl_tables(W, F, states) - want['map_logjoint']) < 1e-10
 
 
-ORACLE_CASES = [(2, 1, (), 'markov'), (2, 2, (), 'minlength'), (2, 3, (), 'markov'), (2, 63, (5,), 'markov'),
-                (2, 64, (), 'minlength'), (2, 65, (10, 40), 'markov'), (3, 65, (7,), 'minlength'), (2, 130, (64,), 'minlength'),
-                (2, 193, (3, 100), 'markov'), (3, 193, (), 'markov')]
-
-
-@pytest.mark.parametrize('S,T,missing,kind', ORACLE_CASES)
+@pytest.mark.parametrize('S,T,missing,kind', DC.ORACLE_CASES)
 def test_against_oracle(S, T, missing, kind):
-    rng = np.random.default_rng(1000 * S + T)
-    model = C.random_model(rng, S, T + 8)
-    x = C.random_traj(rng, T, missing)
-    prior = DC.make_prior(kind, rng, S, T + 5)
-    W, F = C.tables(model, x)
+    case = (S, T, missing, kind)
+    model, x, prior, W, F = DC.oracle_case(case)
+    want = DC.oracle_answer(case)
+    print(f"oracle {DC.ORACLE_SECONDS[case]:.1f} s")
     r = bild_amd.exact_dwell(x, model, prior)
-    check_against_oracle(r, DO.solve(W, F, prior), W, F, prior, exact_map=not missing)
+    check_against_oracle(r, want, W, F, prior, exact_map=not missing)
     # the forward pass alone gives the same evidence and MAP, bit for bit
     f = bild_amd.exact_dwell(x, model, prior, marginals=False)
     assert f.log_marginal_posterior is None and f.expected_jumps is None
-    assert f.log_evidence == r.log_evidence and f.map_log_joint == r.map_log_joint and f.map_profile == r.map_profile
+    assert f.log_evidence == r.log_evidence and f.map_profile == r.map_profile
+    assert np.array_equal(f.map_log_joint, r.map_log_joint, equal_nan=True)
+    if kind == 'impossible':
+        assert r.log_evidence == -np.inf and r.map_profile is None and np.isnan(r.map_log_joint)
+        assert np.all(np.isnan(r.log_marginal_posterior)) and r.log_marginal_posterior.shape == (S, T)
+        assert np.all(np.isnan(r.expected_jumps)) and np.all(np.isnan(r.expected_stay))
+        with pytest.raises(ValueError, match='-inf: no profile of positive weight'):
+            r.draw(8)
+    else:
+        assert np.isfinite(r.log_evidence) and r.map_profile is not None
+    if kind == 'flip':
+        assert r.expected_jumps.sum() == pytest.approx(T - 1, abs=1e-9)
+        assert np.all(r.expected_stay <= 1e-12)
+    if S == 1:
+        assert np.array_equal(r.expected_jumps, [[0.0]]) and np.all(r.log_marginal_posterior == 0.0)
+        assert r.map_profile is not None and np.all(np.asarray(r.map_profile[:]) == 0)
+
+
+def test_ragged_batch_against_oracle():
+    """ four states, non-geometric tables, six trajectories in one call: five are shorter than the call's longest """
+    model, prior, xs, tabs = DC.ragged_case()
+    batch = bild_amd.exact_dwell(xs, model, prior)
+    for j, ((T, missing), r, want, (W, F)) in enumerate(zip(DC.RAGGED, batch, DC.ragged_answers(), tabs)):
+        print(f"trajectory {j}, T = {T}, oracle {DC.ORACLE_SECONDS['ragged', j]:.1f} s")
+        assert np.isfinite(want['logev']) and len(r.traj) == T
+        check_against_oracle(r, want, W, F, prior, exact_map=not missing)
+    # one trajectory per chunk
+    chunked = bild_amd.exact_dwell(xs, model, prior, scratch_bytes=1)
+    assert all(same(a, b) for a, b in zip(batch, chunked))
+
+
+def test_sharp_posterior():
+    """
+    Steps that depend on the state 50-fold: W down to -1.1e5, and marginals that the oracle holds down to e^-710 and then at 0.
+    The bars for logev, the MAP log joint and the log marginals are the file's 1e-10 times max|finite W| / 3e3 (about 3.7e-9):
+    1e-10 was set where the summed terms are ~3e3 (the comment in `test_T1000`), and the rounding of an exponent grows with its size.
+    A log marginal whose reference is below -600 or -inf must be -inf or below -590.
+    """
+    model, x, prior, st, W, F = DC.sharp_case()
+    want = DC.sharp_answer()
+    scale = max(1.0, np.max(np.abs(W[np.isfinite(W)])) / 3e3)
+    bar = 1e-10 * scale
+    r = bild_amd.exact_dwell(x, model, prior)
+    assert r.n_nan_windows == 0 == want['n_nan_windows']
+    assert np.array_equal(np.asarray(r.map_profile[:]), st) and np.array_equal(want['map_states'], st)
+    print(f"sharp: oracle {DC.ORACLE_SECONDS['sharp']:.1f} s, min finite W {np.min(W[np.isfinite(W)]):.4g}, scale {scale:.2f}, bar {bar:.3g}")
+    for name, got, ref in (('logev', r.log_evidence, want['logev']), ('map_logjoint', r.map_log_joint, want['map_logjoint'])):
+        print(name, got, ref, abs(got - ref))
+        assert abs(got - ref) < bar, (name, got, ref)
+    got, ref = r.log_marginal_posterior, want['log_post']
+    assert got.shape == ref.shape == (2, len(x)) and not np.any(np.isnan(got)) and not np.any(np.isnan(ref))
+    firm = ref >= -600
+    low = got[~firm]
+    print(f"log_post: {int(firm.sum())} entries at or above -600: worst {np.max(np.abs(got[firm] - ref[firm])):.3e}; {low.size} below "
+          f"(reference -inf on {int(np.sum(ref == -np.inf))}): device -inf on {int(np.sum(low == -np.inf))}, largest other "
+          f"{np.max(low[low > -np.inf], initial=-np.inf):.2f}")
+    assert np.max(np.abs(got[firm] - ref[firm])) < bar
+    assert np.all((low == -np.inf) | (low < -590))
+    for name, got, ref in (('jumps', r.expected_jumps, want['exp_jumps']), ('stay', r.expected_stay, want['exp_stay'])):
+        print(name, np.max(np.abs(got - ref)), np.max(np.abs(got - ref) - 1e-9 * np.abs(ref)))
+        assert np.all(np.abs(got - ref) <= 1e-9 * np.abs(ref) + 1e-12), (name, got, ref)
 
 
 @pytest.mark.parametrize('nan', ['propagate', 'omit'])

@@ -1,6 +1,7 @@
 """
 The draws under a dwell-time prior on the GPU (bild_amd.exact.exact_dwell_draw, csrc/gauss_dwelldraw.hip, DESIGN.md section
-22): replay against the NumPy oracle tests/dwell_draw_oracle.py draw for draw around the 64-lane scan, device mode as replay
+22): replay against the NumPy oracle tests/dwell_draw_oracle.py draw for draw around the 64-lane scan, at one to four states, beyond
+256 frames and under non-geometric and bounded priors, six trajectories in one call, device mode as replay
 of its own uniforms, bit-identity across call shapes, the distribution against the enumeration and against `exact_dwell`'s
 marginals, T = 1000, `posterior_distance`, and the refusals of the C call.
 
@@ -39,22 +40,23 @@ def logl_segments(model, x, d):
 def test_replay_against_oracle(name):
     model, x, prior, u = DDC.replay_case(name)
     want = DDC.oracle_replay(name)
-    fragile = want['fragile']
+    fragile, n = want['fragile'], DDC.n_replay(name)
+    assert len(u) == n == len(fragile)
     # the excused share: a condition on the inputs (tests/test_dwell_draw.py asserts that it is 0 for these seeds)
-    assert fragile.sum() <= 0.001 * DDC.N_REPLAY
+    assert fragile.sum() <= 0.001 * n
     if 'order0' in name:
         r = bild_amd.exact_dwell(x, model, prior)
         assert r.n_nan_windows > 0 and np.isnan(r.log_evidence)
         with pytest.raises(ValueError, match="nan='omit'"):
-            r.draw(DDC.N_REPLAY, uniforms=u)
+            r.draw(n, uniforms=u)
         r = bild_amd.exact_dwell(x, model, prior, nan='omit')
         assert r.n_nan_windows > 0
     else:
         r = bild_amd.exact_dwell(x, model, prior)
-    d = r.draw(DDC.N_REPLAY, uniforms=u)
+    d = r.draw(n, uniforms=u)
     firm = ~fragile
     states = d.states()
-    assert states.shape == (DDC.N_REPLAY, len(x)) and d.T == len(x) and len(d) == DDC.N_REPLAY
+    assert states.shape == (n, len(x)) and d.T == len(x) and len(d) == n
     assert np.array_equal(states[firm], want['states'][firm])
     assert np.array_equal(d.n_switches[firm], want['n_switches'][firm]) and np.array_equal(d.n_uniforms[firm], want['n_uniforms'][firm])
     assert np.array_equal(d.n_uniforms, 1 + 2 * d.n_switches)
@@ -75,6 +77,25 @@ def same_draws(a, b):
     for name in ('n_switches', 'logL', 'log_prior', 'n_uniforms', 'uniforms'):
         assert np.array_equal(getattr(a, name), getattr(b, name)), name
     assert np.array_equal(a.states(), b.states())
+
+
+def test_six_trajectories_in_one_call():
+    """ more than four trajectories: `dwelldraw_head_kernel`'s second workgroup, on a ragged set of four states """
+    model, prior, xs, tabs = DC.ragged_case()
+    n, u = DDC.N_SIX, DDC.six_uniforms()
+    res = bild_amd.exact_dwell(xs, model, prior, marginals=False)
+    together = bild_amd.exact_dwell_draw(res, n, uniforms=u)
+    assert [d.T for d in together] == [T for T, _ in DC.RAGGED]
+    for j, d in enumerate(together):    # a trajectory alone, on a set of its own
+        same_draws(d, bild_amd.exact_dwell(xs[j], model, prior, marginals=False).draw(n, uniforms=u[j]))
+        assert np.array_equal(d.n_uniforms, 1 + 2 * d.n_switches) and np.max(np.abs(d.logL - logl_segments(model, xs[j], d))) < 1e-10
+    for j in (1, 5):
+        want = DDC.oracle_six(j)
+        firm = ~want['fragile']
+        print(f"trajectory {j}: fragile {int(want['fragile'].sum())}, switches {together[j].n_switches.min()} ... {together[j].n_switches.max()}")
+        assert want['fragile'].sum() <= 1
+        assert np.array_equal(together[j].states()[firm], want['states'][firm])
+        assert np.array_equal(together[j].n_switches[firm], want['n_switches'][firm])
 
 
 def test_device_mode_is_replay_of_its_own_uniforms():
