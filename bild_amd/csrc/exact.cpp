@@ -3,10 +3,10 @@
 #include <functional>
 #include <limits>
 
-#include "likelihood.h"
 #include "exact.h"
 #include "gauss.h"
-#include "internal.h"
+#include "gauss_call.h"
+#include "gauss_segdp.h"
 
 namespace {
 
@@ -111,38 +111,6 @@ void unrank(int64_t L, int T, int k, int64_t C, const std::vector<int32_t> &trac
     }
 }
 
-int check_transitions(int S, const uint8_t *transitions)
-{
-    if (!transitions) return fail(BILD_ERR_INVALID, "transitions is NULL");
-    for (int i = 0; i < S * S; ++i)
-        if (transitions[i] > 1) return fail(BILD_ERR_INVALID, "transitions[%d] = %d; must be 0 or 1", i, transitions[i]);
-    return BILD_OK;
-}
-
-// Device memory of one call, freed on every path
-struct Bufs {
-    std::vector<void *> ptrs;
-    ~Bufs()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class X> int alloc(X **out, size_t count)
-    {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(X));
-        if (e != hipSuccess) return fail(BILD_ERR_NOMEM, "hipMalloc(%zu) failed: %s", count * sizeof(X), hipGetErrorString(e));
-        ptrs.push_back(p);
-        *out = static_cast<X *>(p);
-        return BILD_OK;
-    }
-};
-
-#define EX_TRY(x)                       \
-    do {                                \
-        int rc_ = (x);                  \
-        if (rc_ != BILD_OK) return rc_; \
-    } while (0)
-
 // What the refusals leave for the device part
 struct Plan {
     int n_traj = 0, S = 0, k = 0, Tm = 1;
@@ -159,7 +127,7 @@ int plan_call(int n_traj, const int *T, int S, int k, const uint8_t *transitions
 {
     if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
     if (k < 0 || k > kExactMaxK) return fail(BILD_ERR_UNSUPPORTED, "k = %d: exact enumeration supports 0 <= k <= %d", k, kExactMaxK);
-    EX_TRY(check_transitions(S, transitions));
+    BILD_TRY(segdp_check_transitions(S, transitions));
     if (!(max_profiles >= 0)) return fail(BILD_ERR_INVALID, "max_profiles must be a non-negative number");
     if (scratch_bytes < 0) return fail(BILD_ERR_INVALID, "scratch_bytes = %lld is negative", (long long)scratch_bytes);
     p->n_traj = n_traj;
@@ -195,9 +163,13 @@ int plan_call(int n_traj, const int *T, int S, int k, const uint8_t *transitions
 
 using Eval = std::function<int(int64_t rows, const int32_t *d_ss, const int32_t *d_sv, const int32_t *d_tid, double *d_out)>;
 
-// the device part: plan of blocks and chunks, one pass per chunk, results to `out`
-int run_exact(const Plan &p, int64_t scratch_bytes, int T_max, hipStream_t st, const Eval &eval, bild_exact_out *out)
+// the device part: plan of blocks and chunks, one pass per chunk, results to `out`.  On `st`, under `held` where the stream
+// is shared.
+int run_exact(const Plan &p, int64_t scratch_bytes, int T_max, hipStream_t st, std::unique_lock<std::mutex> held, const Eval &eval,
+              bild_exact_out *out)
 {
+    CallFrame call;
+    call.open(st, std::move(held));
     const int k = p.k, K1 = k + 1, S = p.S, n_traj = p.n_traj, Tm = p.Tm;
     const bool marg = p.marginals;
 
@@ -208,13 +180,9 @@ int run_exact(const Plan &p, int64_t scratch_bytes, int T_max, hipStream_t st, c
             blocks.push_back(ExactBlock{l0, 0, j, (int32_t)std::min<int64_t>(kExactBlock, p.count[j] - l0)});
     const int64_t nblocks = (int64_t)blocks.size();
     const int64_t per_block = (int64_t)kExactBlock * (8 * K1 + 4 + 8) + (int64_t)sizeof(ExactPart) + (marg ? (int64_t)S * Tm * 8 : 0);
-    int64_t budget = scratch_bytes;
-    if (budget == 0) {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        budget = std::min<int64_t>((int64_t)1 << 30, (int64_t)(free_b / 3));
-    }
-    const int64_t chunk_blocks = std::max<int64_t>(1, std::min<int64_t>(budget / per_block, 1 << 20));
+    int chunk = 0;
+    BILD_TRY(call.chunk_of(per_block, scratch_bytes, 1 << 20, &chunk));
+    const int64_t chunk_blocks = chunk;
     struct Chunk {
         int64_t b0, nb, rows, r0, nr;   // blocks [b0, b0 + nb), rows, runs [r0, r0 + nr)
     };
@@ -239,11 +207,6 @@ int run_exact(const Plan &p, int64_t scratch_bytes, int T_max, hipStream_t st, c
 
     const int A = std::max(1, Tm - 1);
     const std::vector<uint64_t> binom = binom_table(A, k);
-    Bufs bufs;
-    struct Drain {      // (declared after the buffers: on an error path the stream is drained before they are freed)
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{st};
     ExactBlock *d_blocks;
     ExactRun *d_runs;
     uint64_t *d_binom;
@@ -252,21 +215,21 @@ int run_exact(const Plan &p, int64_t scratch_bytes, int T_max, hipStream_t st, c
     ExactAcc *d_acc;
     ExactPart *d_part;
     double *d_logl, *d_marg = nullptr, *d_acc_marg = nullptr;
-    EX_TRY(bufs.alloc(&d_blocks, blocks.size()));
-    EX_TRY(bufs.alloc(&d_runs, runs.size()));
-    EX_TRY(bufs.alloc(&d_binom, binom.size()));
-    EX_TRY(bufs.alloc(&d_traces, p.traces.size()));
-    EX_TRY(bufs.alloc(&d_T, n_traj));
-    EX_TRY(bufs.alloc(&d_ncomb, n_traj));
-    EX_TRY(bufs.alloc(&d_acc, n_traj));
-    EX_TRY(bufs.alloc(&d_ss, (size_t)max_rows * K1));
-    EX_TRY(bufs.alloc(&d_sv, (size_t)max_rows * K1));
-    EX_TRY(bufs.alloc(&d_tid, (size_t)max_rows));
-    EX_TRY(bufs.alloc(&d_logl, (size_t)max_rows));
-    EX_TRY(bufs.alloc(&d_part, (size_t)max_nb));
+    BILD_TRY(call.alloc(&d_blocks, blocks.size()));
+    BILD_TRY(call.alloc(&d_runs, runs.size()));
+    BILD_TRY(call.alloc(&d_binom, binom.size()));
+    BILD_TRY(call.alloc(&d_traces, p.traces.size()));
+    BILD_TRY(call.alloc(&d_T, n_traj));
+    BILD_TRY(call.alloc(&d_ncomb, n_traj));
+    BILD_TRY(call.alloc(&d_acc, n_traj));
+    BILD_TRY(call.alloc(&d_ss, (size_t)max_rows * K1));
+    BILD_TRY(call.alloc(&d_sv, (size_t)max_rows * K1));
+    BILD_TRY(call.alloc(&d_tid, (size_t)max_rows));
+    BILD_TRY(call.alloc(&d_logl, (size_t)max_rows));
+    BILD_TRY(call.alloc(&d_part, (size_t)max_nb));
     if (marg) {
-        EX_TRY(bufs.alloc(&d_marg, (size_t)max_nb * S * Tm));
-        EX_TRY(bufs.alloc(&d_acc_marg, (size_t)n_traj * S * Tm));
+        BILD_TRY(call.alloc(&d_marg, (size_t)max_nb * S * Tm));
+        BILD_TRY(call.alloc(&d_acc_marg, (size_t)n_traj * S * Tm));
         HIP_TRY(hipMemsetAsync(d_acc_marg, 0, (size_t)n_traj * S * Tm * 8, st));
     }
     std::vector<ExactAcc> acc(n_traj, ExactAcc{-std::numeric_limits<double>::infinity(), 0.0, 0.0,
@@ -294,7 +257,7 @@ int run_exact(const Plan &p, int64_t scratch_bytes, int T_max, hipStream_t st, c
         e.k = k;
         e.A = A;
         if (launch_exact_enumerate(e, st)) return fail(BILD_ERR_HIP, "launch of the enumeration kernel failed");
-        EX_TRY(eval(c.rows, d_ss, d_sv, d_tid, d_logl));
+        BILD_TRY(eval(c.rows, d_ss, d_sv, d_tid, d_logl));
         ExactReduce r{};
         r.blocks = d_blocks + c.b0;
         r.logl = d_logl;
@@ -371,7 +334,7 @@ int bild_exact_count(int T, int k, int S, const uint8_t *transitions, double *n_
     if (T < 1) return fail(BILD_ERR_INVALID, "T = %d must be positive", T);
     if (S < 1) return fail(BILD_ERR_INVALID, "S = %d must be positive", S);
     if (k < 0 || k > kExactMaxK) return fail(BILD_ERR_UNSUPPORTED, "k = %d: exact enumeration supports 0 <= k <= %d", k, kExactMaxK);
-    EX_TRY(check_transitions(S, transitions));
+    BILD_TRY(segdp_check_transitions(S, transitions));
     *n_profiles = binom_double(T - 1, k) * trace_count(S, transitions, k);
     return BILD_OK;
 }
@@ -384,7 +347,7 @@ int bild_exact_evidence(const bild_model *m, const bild_trajset *ts, int k, cons
     std::vector<int> T(ts->n_traj);
     for (int j = 0; j < ts->n_traj; ++j) T[j] = ts->descs[j].T;
     Plan p;
-    EX_TRY(plan_call(ts->n_traj, T.data(), m->S, k, transitions, max_profiles, scratch_bytes, T_max, out, &p));
+    BILD_TRY(plan_call(ts->n_traj, T.data(), m->S, k, transitions, max_profiles, scratch_bytes, T_max, out, &p));
     int64_t total = 0;
     for (int64_t c : p.count) total += c;
     // a set that has not been evaluated yet and sees 1e8 evaluations here: the state table may take its larger budget
@@ -392,12 +355,12 @@ int bild_exact_evidence(const bild_model *m, const bild_trajset *ts, int k, cons
         ts->expected_evals = total;
     hipStream_t st = (hipStream_t)internal_model_stream(m);
     if (!st) return BILD_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lock(m->call_mu);     // the model's stream: one call at a time, as for the host-buffer calls
     const int K1 = k + 1;
     auto eval = [&](int64_t rows, const int32_t *d_ss, const int32_t *d_sv, const int32_t *d_tid, double *d_out) {
         return bild_logl_segments_device(m, ts, rows, K1, d_ss, d_sv, d_tid, flags & 0xfu, (void *)st, d_out);
     };
-    return run_exact(p, scratch_bytes, T_max, st, eval, out);
+    // the model's stream: one call at a time, as for the host-buffer calls
+    return run_exact(p, scratch_bytes, T_max, st, std::unique_lock<std::mutex>(m->call_mu), eval, out);
 }
 
 int bild_gauss_exact_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k, const uint8_t *transitions,
@@ -405,9 +368,9 @@ int bild_gauss_exact_evidence(const bild_gauss_model *m, const bild_gauss_trajse
 {
     int n_traj = 0;
     const int *T = nullptr;
-    EX_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
+    BILD_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
     Plan p;
-    EX_TRY(plan_call(n_traj, T, m->S, k, transitions, max_profiles, scratch_bytes, T_max, out, &p));
+    BILD_TRY(plan_call(n_traj, T, m->S, k, transitions, max_profiles, scratch_bytes, T_max, out, &p));
     hipStream_t st = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     struct StreamGuard {
@@ -418,7 +381,7 @@ int bild_gauss_exact_evidence(const bild_gauss_model *m, const bild_gauss_trajse
     auto eval = [&](int64_t rows, const int32_t *d_ss, const int32_t *d_sv, const int32_t *d_tid, double *d_out) {
         return internal_gauss_walk_resident(m, ts, rows, K1, d_ss, d_sv, d_tid, d_out, (void *)st);
     };
-    return run_exact(p, scratch_bytes, T_max, st, eval, out);
+    return run_exact(p, scratch_bytes, T_max, st, std::unique_lock<std::mutex>(), eval, out);     // a stream of the call's own
 }
 
 } // extern "C"

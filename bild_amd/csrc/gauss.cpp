@@ -43,12 +43,6 @@ struct BuildBufs {
     }
 };
 
-#define GAUSS_TRY(x)                  \
-    do {                              \
-        int rc_ = (x);                \
-        if (rc_ != BILD_OK) return rc_; \
-    } while (0)
-
 // The tables of one trajectory (x: T x d, NaN = missing) into W / F.  Dimensions in index order; per dimension and state:
 // the shared factor of the valid tail, the starts inside it (solve), the others (per-start factorisation, in chunks of
 // `slots` scratch slots).
@@ -118,11 +112,11 @@ int build_one(const bild_gauss_model *m, int T, const double *x, const double *d
     int32_t *d_vidx, *d_rank, *d_order;
     double *d_xv;
     GaussJob *d_jobs;
-    GAUSS_TRY(bufs.alloc(&d_vidx, vidx.size()));
-    GAUSS_TRY(bufs.alloc(&d_rank, rank.size()));
-    GAUSS_TRY(bufs.alloc(&d_order, order_d.size()));
-    GAUSS_TRY(bufs.alloc(&d_xv, xv.size()));
-    GAUSS_TRY(bufs.alloc(&d_jobs, jobs.size()));
+    BILD_TRY(bufs.alloc(&d_vidx, vidx.size()));
+    BILD_TRY(bufs.alloc(&d_rank, rank.size()));
+    BILD_TRY(bufs.alloc(&d_order, order_d.size()));
+    BILD_TRY(bufs.alloc(&d_xv, xv.size()));
+    BILD_TRY(bufs.alloc(&d_jobs, jobs.size()));
     HIP_TRY(hipMemcpyAsync(d_vidx, vidx.data(), vidx.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(d_rank, rank.data(), rank.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(d_order, order_d.data(), order_d.size() * 4, hipMemcpyHostToDevice, stream));
@@ -217,9 +211,9 @@ int run_walk(bild_gauss_trajset *ts, GaussWalk &w, bool st, std::initializer_lis
     std::lock_guard<std::mutex> lock(ts->mu);
     size_t total = 256;     // status
     for (const Part &pp : parts) total += (pp.bytes + 255) & ~size_t(255);
-    GAUSS_TRY(ts->d_in.reserve(total));
-    GAUSS_TRY(ts->d_out.reserve((size_t)w.n * 8));
-    GAUSS_TRY(ts->h_out.reserve((size_t)w.n * 8 + 8));
+    BILD_TRY(ts->d_in.reserve(total));
+    BILD_TRY(ts->d_out.reserve((size_t)w.n * 8));
+    BILD_TRY(ts->h_out.reserve((size_t)w.n * 8 + 8));
     char *base = static_cast<char *>(ts->d_in.ptr);
     size_t off = 0;
     for (const Part &pp : parts) {
@@ -365,17 +359,17 @@ int bild_gauss_trajset_create(const bild_gauss_model *m, int n_traj, const int32
     const auto t_start = std::chrono::steady_clock::now();
     BuildBufs bufs;
     double *d_msd, *d_tau, *d_factor, *d_scratch;
-    GAUSS_TRY(bufs.alloc(&d_msd, m->msd.size()));
+    BILD_TRY(bufs.alloc(&d_msd, m->msd.size()));
     HIP_TRY(hipMemcpyAsync(d_msd, m->msd.data(), m->msd.size() * 8, hipMemcpyHostToDevice, ts->stream));
-    GAUSS_TRY(bufs.alloc(&d_tau, (size_t)S * (Tmax + 1) * Tmax));
-    GAUSS_TRY(bufs.alloc(&d_factor, (size_t)Tmax * Tmax));
+    BILD_TRY(bufs.alloc(&d_tau, (size_t)S * (Tmax + 1) * Tmax));
+    BILD_TRY(bufs.alloc(&d_factor, (size_t)Tmax * Tmax));
     // per-start factorisation scratch: at most 1 GiB and at most a third of the free memory, no more than all starts need
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     const int64_t slot_max = (int64_t)(Tmax + 1) * Tmax;
     int64_t scratch_doubles = std::min<int64_t>({(int64_t)(1ll << 30) / 8, (int64_t)(free_b / 3) / 8, slot_max * Tmax});
     scratch_doubles = std::max<int64_t>(scratch_doubles, slot_max);    // at least one slot, else the build cannot run
-    GAUSS_TRY(bufs.alloc(&d_scratch, (size_t)scratch_doubles));
+    BILD_TRY(bufs.alloc(&d_scratch, (size_t)scratch_doubles));
 
     std::vector<GaussTraj> desc(n_traj);
     const double *xj = x;
@@ -383,7 +377,7 @@ int bild_gauss_trajset_create(const bild_gauss_model *m, int n_traj, const int32
         double *W = ts->tables + off[j];
         double *F = W + (int64_t)S * gauss_w_per_state(T[j]);
         desc[j] = GaussTraj{W, F, gauss_w_per_state(T[j]), T[j]};
-        GAUSS_TRY(build_one(m, T[j], xj, d_msd, W, F, d_tau, d_factor, d_scratch, scratch_doubles, bufs, ts->stream));
+        BILD_TRY(build_one(m, T[j], xj, d_msd, W, F, d_tau, d_factor, d_scratch, scratch_doubles, bufs, ts->stream));
         xj += (size_t)T[j] * d;
     }
     HIP_TRY(hipMemcpyAsync(ts->d_trajs, desc.data(), sizeof(GaussTraj) * n_traj, hipMemcpyHostToDevice, ts->stream));
@@ -407,7 +401,7 @@ int bild_gauss_trajset_info(const bild_gauss_trajset *ts, int64_t *table_bytes, 
 int bild_gauss_logl_segments(const bild_gauss_model *m, const bild_gauss_trajset *ts, int64_t n, int K1, const int32_t *seg_start,
                              const int32_t *seg_state, const int32_t *traj_id, double *out)
 {
-    GAUSS_TRY(check_eval(m, ts, n, K1, traj_id, out));
+    BILD_TRY(check_eval(m, ts, n, K1, traj_id, out));
     if (n == 0) return BILD_OK;
     if (!seg_start || !seg_state) return fail(BILD_ERR_INVALID, "NULL segment arrays");
     for (int64_t r = 0; r < n; ++r) {
@@ -424,7 +418,7 @@ int bild_gauss_logl_segments(const bild_gauss_model *m, const bild_gauss_trajset
     w.K1 = K1;
     w.S = m->S;
     int32_t status[2] = {0, 0};
-    GAUSS_TRY(run_walk(const_cast<bild_gauss_trajset *>(ts), w, false,
+    BILD_TRY(run_walk(const_cast<bild_gauss_trajset *>(ts), w, false,
                        {{seg_start, (size_t)n * K1 * 4, (const void **)&w.seg_start},
                         {seg_state, (size_t)n * K1 * 4, (const void **)&w.seg_state},
                         {traj_id, traj_id ? (size_t)n * 4 : 0, (const void **)&w.traj_id}},
@@ -435,7 +429,7 @@ int bild_gauss_logl_segments(const bild_gauss_model *m, const bild_gauss_trajset
 int bild_gauss_logl_st(const bild_gauss_model *m, const bild_gauss_trajset *ts, int64_t n, int K1, const double *ss,
                        const int64_t *thetas, const int32_t *traj_id, double *out)
 {
-    GAUSS_TRY(check_eval(m, ts, n, K1, traj_id, out));
+    BILD_TRY(check_eval(m, ts, n, K1, traj_id, out));
     if (n == 0) return BILD_OK;
     if (!ss || !thetas) return fail(BILD_ERR_INVALID, "NULL ss / thetas");
     GaussWalk w{};
@@ -443,7 +437,7 @@ int bild_gauss_logl_st(const bild_gauss_model *m, const bild_gauss_trajset *ts, 
     w.K1 = K1;
     w.S = m->S;
     int32_t status[2] = {0, 0};
-    GAUSS_TRY(run_walk(const_cast<bild_gauss_trajset *>(ts), w, true,
+    BILD_TRY(run_walk(const_cast<bild_gauss_trajset *>(ts), w, true,
                        {{ss, (size_t)n * K1 * 8, (const void **)&w.ss},
                         {thetas, (size_t)n * K1 * 8, (const void **)&w.thetas},
                         {traj_id, traj_id ? (size_t)n * 4 : 0, (const void **)&w.traj_id}},

@@ -1,40 +1,15 @@
 // Exact inference under a dwell-time prior (include/bild_amd.h, "exact inference under a dwell-time prior"; DESIGN.md
-// section 21): the refusals, the chunks of whole trajectories, the launches on the set's stream, and the NaN rule on what
-// comes back.  Kernels: gauss_dwell.hip.
+// section 21): the refusals and the upload of the prior (gauss_dwelldraw.cpp's as well), the chunks of whole trajectories,
+// the launches on the set's stream, and the NaN rule on what comes back.  Kernels: gauss_dwell.hip.
 #include <cmath>
 #include <limits>
 
-#include "likelihood.h"
+#include "gauss_call.h"
 #include "gauss_dwell.h"
-#include "internal.h"
 
 namespace {
 
 using namespace bild;
-
-#define DW_TRY(x)                       \
-    do {                                \
-        int rc_ = (x);                  \
-        if (rc_ != BILD_OK) return rc_; \
-    } while (0)
-
-// Device memory of one call, freed on every path
-struct Bufs {
-    std::vector<void *> ptrs;
-    ~Bufs()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class X> int alloc(X **out, size_t count)
-    {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(X));
-        if (e != hipSuccess) return fail(BILD_ERR_NOMEM, "hipMalloc(%zu) failed: %s", count * sizeof(X), hipGetErrorString(e));
-        ptrs.push_back(p);
-        *out = static_cast<X *>(p);
-        return BILD_OK;
-    }
-};
 
 // finite or -inf
 int check_logs(const char *name, const double *a, size_t n)
@@ -55,10 +30,10 @@ int dwell_check_call(int S, int L, const double *log_init, const double *log_jum
 {
     if (S > kDwellMaxS) return fail(BILD_ERR_UNSUPPORTED, "the model has %d states; the dwell-time recursion supports at most %d", S, kDwellMaxS);
     if (L < 1) return fail(BILD_ERR_INVALID, "L = %d: the dwell tables need at least one length", L);
-    DW_TRY(check_logs("log_init", log_init, (size_t)S));
-    DW_TRY(check_logs("log_jump", log_jump, (size_t)S * S));
-    DW_TRY(check_logs("log_dwell", log_dwell, (size_t)S * L));
-    DW_TRY(check_logs("log_surv", log_surv, (size_t)S * L));
+    BILD_TRY(check_logs("log_init", log_init, (size_t)S));
+    BILD_TRY(check_logs("log_jump", log_jump, (size_t)S * S));
+    BILD_TRY(check_logs("log_dwell", log_dwell, (size_t)S * L));
+    BILD_TRY(check_logs("log_surv", log_surv, (size_t)S * L));
     bool any_init = false;
     for (int s = 0; s < S; ++s) {
         if (!std::isinf(log_jump[s * S + s]))
@@ -75,6 +50,22 @@ int dwell_check_call(int S, int L, const double *log_init, const double *log_jum
     return BILD_OK;
 }
 
+int dwell_upload_prior(CallFrame &call, int S, int L, const double *log_init, const double *log_jump, const double *log_dwell,
+                       const double *log_surv, DwellPrior *prior)
+{
+    const size_t n_jump = (size_t)S * S, n_len = (size_t)S * L;
+    std::vector<double> host(S + n_jump + 2 * n_len);
+    std::copy_n(log_init, S, host.data());
+    std::copy_n(log_jump, n_jump, host.data() + S);
+    std::copy_n(log_dwell, n_len, host.data() + S + n_jump);
+    std::copy_n(log_surv, n_len, host.data() + S + n_jump + n_len);
+    double *d = nullptr;
+    BILD_TRY(call.alloc(&d, host.size()));
+    HIP_TRY(hipMemcpy(d, host.data(), host.size() * 8, hipMemcpyHostToDevice));     // (synchronous: `host` ends here)
+    *prior = DwellPrior{d, d + S, d + S + n_jump, d + S + n_jump + n_len};
+    return BILD_OK;
+}
+
 } // namespace bild
 
 extern "C" int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
@@ -83,11 +74,11 @@ extern "C" int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_g
 {
     int n_traj = 0;
     const int *T = nullptr;
-    DW_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
+    BILD_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
     if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
     if (flags & ~BILD_DWELL_NAN_OMIT) return fail(BILD_ERR_INVALID, "flags = %u: unknown bits", flags);
     const int S = m->S;
-    DW_TRY(dwell_check_call(S, L, log_init, log_jump, log_dwell, log_surv, n_traj, T, T_max, scratch_bytes));
+    BILD_TRY(dwell_check_call(S, L, log_init, log_jump, log_dwell, log_surv, n_traj, T, T_max, scratch_bytes));
     int Tm = 1;
     for (int j = 0; j < n_traj; ++j) Tm = std::max(Tm, T[j]);
     if (n_traj == 0) return BILD_OK;
@@ -96,61 +87,40 @@ extern "C" int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_g
     const int ld = Tm + 1, ntile = (Tm + kDwellTile - 1) / kDwellTile;
     const int64_t slot = (int64_t)S * ld, rows = (int64_t)S * ntile * Tm;
 
-    const GaussTraj *d_trajs = nullptr;
-    void *stream = nullptr;
-    std::mutex *mu = nullptr;
-    DW_TRY(internal_gauss_set_device(m, ts, &d_trajs, &stream, &mu));
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(*mu);      // the set's stream: one call at a time
+    CallFrame call;
+    BILD_TRY(call.open(m, ts));
+    hipStream_t st = call.st;
 
-    // chunks of whole trajectories within the budget (at least one)
     const int64_t per_traj = slot * (4 * 8 + 2 * 4 + (stats ? 4 * 8 : 0)) + (stats ? (rows + (int64_t)S * ntile + S * S + S) * 8 : 0) + Tm + 24;
-    int64_t budget = scratch_bytes;
-    if (budget == 0) {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        budget = std::min<int64_t>((int64_t)1 << 30, (int64_t)(free_b / 3));
-    }
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(budget / per_traj, n_traj));
+    int chunk = 0;
+    BILD_TRY(call.chunk_of(per_traj, scratch_bytes, n_traj, &chunk));
 
-    Bufs bufs;
-    struct Drain {      // (declared after the buffers: on an error path the stream is drained before they are freed)
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{st};
     DwellParams p{};
-    double *d_prior = nullptr;
-    const size_t n_prior = (size_t)S + (size_t)S * S + 2 * (size_t)S * L;
-    DW_TRY(bufs.alloc(&d_prior, n_prior));
-    DW_TRY(bufs.alloc(&p.A, (size_t)chunk * slot));
-    DW_TRY(bufs.alloc(&p.AV, (size_t)chunk * slot));
-    DW_TRY(bufs.alloc(&p.alpha, (size_t)chunk * slot));
-    DW_TRY(bufs.alloc(&p.alphaV, (size_t)chunk * slot));
-    DW_TRY(bufs.alloc(&p.Aarg, (size_t)chunk * slot));
-    DW_TRY(bufs.alloc(&p.alphaArg, (size_t)chunk * slot));
-    DW_TRY(bufs.alloc(&p.fin, (size_t)chunk * 2));
-    DW_TRY(bufs.alloc(&p.n_nan, (size_t)chunk));
-    DW_TRY(bufs.alloc(&p.map_states, (size_t)chunk * Tm));
+    DwellPrior dp{};
+    BILD_TRY(dwell_upload_prior(call, S, L, log_init, log_jump, log_dwell, log_surv, &dp));
+    BILD_TRY(call.alloc(&p.A, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.AV, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.alpha, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.alphaV, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.Aarg, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.alphaArg, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.fin, (size_t)chunk * 2));
+    BILD_TRY(call.alloc(&p.n_nan, (size_t)chunk));
+    BILD_TRY(call.alloc(&p.map_states, (size_t)chunk * Tm));
     if (stats) {
-        DW_TRY(bufs.alloc(&p.beta, (size_t)chunk * slot));
-        DW_TRY(bufs.alloc(&p.gamma, (size_t)chunk * slot));
-        DW_TRY(bufs.alloc(&p.cover, (size_t)chunk * slot));
-        DW_TRY(bufs.alloc(&p.post, (size_t)chunk * slot));
-        DW_TRY(bufs.alloc(&p.row_tot, (size_t)chunk * rows));
-        DW_TRY(bufs.alloc(&p.stay_part, (size_t)chunk * S * ntile));
-        DW_TRY(bufs.alloc(&p.jumps, (size_t)chunk * S * S));
-        DW_TRY(bufs.alloc(&p.stay, (size_t)chunk * S));
+        BILD_TRY(call.alloc(&p.beta, (size_t)chunk * slot));
+        BILD_TRY(call.alloc(&p.gamma, (size_t)chunk * slot));
+        BILD_TRY(call.alloc(&p.cover, (size_t)chunk * slot));
+        BILD_TRY(call.alloc(&p.post, (size_t)chunk * slot));
+        BILD_TRY(call.alloc(&p.row_tot, (size_t)chunk * rows));
+        BILD_TRY(call.alloc(&p.stay_part, (size_t)chunk * S * ntile));
+        BILD_TRY(call.alloc(&p.jumps, (size_t)chunk * S * S));
+        BILD_TRY(call.alloc(&p.stay, (size_t)chunk * S));
     }
-    std::vector<double> prior(n_prior);
-    std::copy_n(log_init, S, prior.data());
-    std::copy_n(log_jump, (size_t)S * S, prior.data() + S);
-    std::copy_n(log_dwell, (size_t)S * L, prior.data() + S + S * S);
-    std::copy_n(log_surv, (size_t)S * L, prior.data() + S + S * S + (size_t)S * L);
-    HIP_TRY(hipMemcpy(d_prior, prior.data(), n_prior * 8, hipMemcpyHostToDevice));
-    p.log_init = d_prior;
-    p.log_jump = d_prior + S;
-    p.log_dwell = d_prior + S + S * S;
-    p.log_surv = p.log_dwell + (size_t)S * L;
+    p.log_init = dp.log_init;
+    p.log_jump = dp.log_jump;
+    p.log_dwell = dp.log_dwell;
+    p.log_surv = dp.log_surv;
     p.slot = slot;
     p.S = S;
     p.L = L;
@@ -166,7 +136,7 @@ extern "C" int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_g
 
     for (int j0 = 0; j0 < n_traj; j0 += chunk) {
         const int nc = std::min(chunk, n_traj - j0);
-        p.trajs = d_trajs + j0;
+        p.trajs = call.d_trajs + j0;
         p.n_traj = nc;
         if (launch_dwell_forward(p, st)) return fail(BILD_ERR_HIP, "launch of the forward pass of the dwell-time recursion failed");
         if (stats) {

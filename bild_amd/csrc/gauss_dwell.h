@@ -49,6 +49,15 @@ struct DwellParams {
 int dwell_check_call(int S, int L, const double *log_init, const double *log_jump, const double *log_dwell, const double *log_surv,
                      int n_traj, const int *T, int T_max, int64_t scratch_bytes);
 
+// The four prior tables in one device block: packed, allocated through the frame and uploaded by a synchronous copy.  The
+// device pointers in *prior.  A BILD_* code.
+struct CallFrame;
+struct DwellPrior {
+    const double *log_init, *log_jump, *log_dwell, *log_surv;
+};
+int dwell_upload_prior(CallFrame &call, int S, int L, const double *log_init, const double *log_jump, const double *log_dwell,
+                       const double *log_surv, DwellPrior *prior);
+
 int launch_dwell_forward(const DwellParams &p, void *stream);
 int launch_dwell_backward(const DwellParams &p, void *stream);
 int launch_dwell_cover(const DwellParams &p, void *stream);

@@ -13,23 +13,21 @@
 //   * dwell_backward_kernel: the same tiles, descending.  Part 1: one wave per row a of the tile against gamma(b) right of the
 //       tile, lanes stride b, butterfly merges.  Part 2, wave 0: rows a descending, lane = b holds gamma(b, .) in registers,
 //       a butterfly over the tile's lanes gives beta(a, .), from which lane a gets its gamma(a, .).
-//   * dwell_cover_kernel / dwell_carry_kernel: the statistics, section 18's pattern with one exp per (a, b, s).  The weight
-//       of a segment [a, b) in state s is Q = exp(alpha(a, s) + omega + W + gamma(b, s) - log evidence); frame t collects Q of
-//       every a <= t < b, and Q (b - a - 1) adds up to the expected stays.  Sums of non-negative terms only.
+//   * dwell_cover_kernel / dwell_carry_kernel: the statistics, section 18's pattern (the scans and the carry: wave.h) with
+//       one exp per (a, b, s).  The weight of a segment [a, b) in state s is Q = exp(alpha(a, s) + omega + W + gamma(b, s) -
+//       log evidence); frame t collects Q of every a <= t < b, and Q (b - a - 1) adds up to the expected stays.  Sums of
+//       non-negative terms only.
 //   * dwell_counts_kernel: the expected jumps, O(S^2 T), and the tiles' stays added in tile order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gauss_dwell.h"
+#include "wave.h"
 
 namespace bild {
 namespace {
 
 constexpr int kWaves = kDwellWaves;
-
-__device__ __forceinline__ double neg_inf() { return __longlong_as_double(0xfff0000000000000ll); }
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) { return __shfl_xor(v, mask, 64); }
 
 // (m, z) += exp(t): z counts in units of exp(m)
 __device__ __forceinline__ void lse_add(double &m, double &z, double t)
@@ -223,7 +221,7 @@ template <int S> __global__ void __launch_bounds__(kWaves * 64) dwell_forward_ke
         __syncthreads();    // the tile's tables are in memory before the next tile reads them
     }
 
-    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    cnt = wave_sum(cnt);
     if (lane == 0) sh_cnt[q] = cnt;
     __syncthreads();
     if (threadIdx.x != 0) return;
@@ -287,7 +285,7 @@ template <int S> __global__ void __launch_bounds__(kWaves * 64) dwell_backward_k
                         lse_add(m, z, om + w + g);
                     }
                 }
-                for (int off = 32; off >= 1; off >>= 1) lse_merge(m, z, shfl_xor_f64(m, off), shfl_xor_f64(z, off));
+                for (int off = 32; off >= 1; off >>= 1) lse_merge(m, z, __shfl_xor(m, off, 64), __shfl_xor(z, off, 64));
                 if (lane == 0) sh_m[s][r] = m, sh_z[s][r] = z;
             }
         }
@@ -308,10 +306,8 @@ template <int S> __global__ void __launch_bounds__(kWaves * 64) dwell_backward_k
                         const double w = td.W[(int64_t)s * td.w_per_state + gauss_wrow(T, a - 1) + (f - a)];
                         if (om > neg_inf() && w == w) t = om + w + g[s];
                     }
-                    double m = t;
-                    for (int off = 32; off >= 1; off >>= 1) m = fmax(m, shfl_xor_f64(m, off));
-                    double z = t > neg_inf() ? exp(t - m) : 0.0;
-                    for (int off = 32; off >= 1; off >>= 1) z += shfl_xor_f64(z, off);
+                    double m = wave_max(t);
+                    double z = wave_sum(t > neg_inf() ? exp(t - m) : 0.0);
                     lse_merge(m, z, sh_m[s][la], sh_z[s][la]);
                     bc[s] = lse_value(m, z);
                 }
@@ -361,21 +357,17 @@ __global__ void __launch_bounds__(kDwellThreads) dwell_cover_kernel(DwellParams 
                 if (om > neg_inf() && w == w) qv = exp(fmin(head + om + w + g - logev, 0.0));
             }
             stay += qv * (double)(b - a - 1);
-            // suffix sum across the lanes: lane l gets the terms of lanes >= l
-            for (int off = 1; off < 64; off <<= 1) {
-                const double up = __shfl_down(qv, off, 64);
-                if (lane + off < 64) qv += up;
-            }
+            qv = wave_scan_down(qv, lane);
             if (t >= a) acc += qv;
             if (lane == 0) row_tot[a] = qv;
         }
     }
     if (mine) p.cover[base + t] = acc;
-    for (int off = 32; off >= 1; off >>= 1) stay += shfl_xor_f64(stay, off);
+    stay = wave_sum(stay);
     if (lane == 0) p.stay_part[((int64_t)traj * p.S + s) * p.ntile + tile] = stay;
 }
 
-// post(t) = cover(t) + sum over the rows a <= t of the totals of the tiles to the right of t's: one wave per (s, tile)
+// post from cover and the row totals (wave_carry): one wave per (s, tile)
 __global__ void __launch_bounds__(kDwellThreads) dwell_carry_kernel(DwellParams p)
 {
     const int traj = blockIdx.z, s = blockIdx.y;
@@ -383,29 +375,9 @@ __global__ void __launch_bounds__(kDwellThreads) dwell_carry_kernel(DwellParams 
     const int lane = threadIdx.x & 63;
     const int tile = (int)blockIdx.x * (kDwellThreads / 64) + (threadIdx.x >> 6);
     if (tile * kDwellTile >= T) return;
-    const int t = tile * kDwellTile + lane;
-    const int ntile = (T + kDwellTile - 1) / kDwellTile;
     const double *__restrict__ row_tot = p.row_tot + ((int64_t)traj * p.S + s) * p.ntile * p.Tm;
     const int64_t base = (int64_t)traj * p.slot + (int64_t)s * p.ld;
-    double carry = 0.0;
-    const bool live = p.fin[2 * traj] > neg_inf();
-    for (int blk = 0; live && blk <= tile; ++blk) {
-        const int a = blk * kDwellTile + lane;
-        double v = 0.0;
-        if (a < T)
-            for (int r = tile + 1; r < ntile; ++r) v += row_tot[(int64_t)r * p.Tm + a];
-        if (blk < tile) {
-            for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_f64(v, off);
-        } else {
-            // rows of the tile itself: row a counts for the frames t >= a
-            for (int off = 1; off < 64; off <<= 1) {
-                const double dn = __shfl_up(v, off, 64);
-                if (lane >= off) v += dn;
-            }
-        }
-        carry += v;
-    }
-    if (t < T) p.post[base + t] = p.cover[base + t] + carry;
+    wave_carry(row_tot, p.cover + base, p.post + base, T, p.Tm, tile, p.fin[2 * traj] > neg_inf(), lane);
 }
 
 // expected jumps s' -> s: sum_c exp(A(c, s') + log_jump[s'][s] + beta(c, s) - log evidence); one wave per trajectory
@@ -425,7 +397,7 @@ __global__ void __launch_bounds__(64) dwell_counts_kernel(DwellParams p)
                     const double a = p.A[base + (int64_t)r * ld + c], bt = p.beta[base + (int64_t)s * ld + c];
                     if (a > neg_inf() && bt > neg_inf()) acc += exp(fmin(a + j + bt - logev, 0.0));
                 }
-            for (int off = 32; off >= 1; off >>= 1) acc += shfl_xor_f64(acc, off);
+            acc = wave_sum(acc);
             if (lane == 0) p.jumps[((int64_t)traj * S + r) * S + s] = acc;
         }
     if (lane != 0) return;
@@ -438,8 +410,6 @@ __global__ void __launch_bounds__(64) dwell_counts_kernel(DwellParams p)
 }
 
 } // namespace
-
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : 1; }
 
 int launch_dwell_forward(const DwellParams &p, void *stream)
 {

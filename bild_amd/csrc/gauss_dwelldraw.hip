@@ -12,20 +12,19 @@
 //     table's own value (beta(t_i, s_i), gamma(t_i, s_{i-1}) for a state pick, or the head's pair), summed in another order
 //     than the scan: where rounding carries the target past the scan's end, the last entry of positive weight is taken.  A
 //     lane of weight 0 never qualifies.  The picks of a state run over S values and are done by every lane alike.  The bytes
-//     of a segment are written by the lanes together as soon as its end is picked, byte x always by lane x mod 64.
+//     of a segment are written by the lanes together as soon as its end is picked, byte x always by lane x mod 64.  The walk
+//     of a pick over the blocks is wave.h's wave_pick, as in gauss_segdraw.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gauss_dwelldraw.h"
 #include "philox.h"
+#include "wave.h"
 
 namespace bild {
 namespace {
 
 constexpr int kThreads = kDwelldrawThreads;
-
-__device__ __forceinline__ double neg_inf() { return __longlong_as_double(0xfff0000000000000ll); }
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // log weight of the entry b of a list: prior term + table entry + what can still follow; a NaN window weighs 0
 __device__ __forceinline__ double entry(double prior, double w, double g) { return w == w ? prior + w + g : neg_inf(); }
@@ -54,10 +53,11 @@ __global__ void __launch_bounds__(kThreads) dwelldraw_head_kernel(DwelldrawParam
             }
         }
         if (pass == 0) {
+            // (wave_max, written out: through the helper the compiler keeps 8 more VGPRs here, a wave less per SIMD)
             for (int off = 32; off >= 1; off >>= 1) best = fmax(best, __shfl_xor(best, off, 64));
             if (!(best > neg_inf())) break;
         } else {
-            for (int off = 32; off >= 1; off >>= 1) z += __shfl_xor(z, off, 64);
+            z = wave_sum(z);
         }
     }
     if (lane == 0) {
@@ -73,25 +73,10 @@ __device__ __forceinline__ int dwelldraw_pick(const double *__restrict__ row, co
                                               const double *__restrict__ gam, int lo, int T, double shift, double target, int lane,
                                               double &base, int &last)
 {
-    for (int b0 = lo; b0 <= T; b0 += 64) {
-        const int b = b0 + lane;
-        double e = 0.0;
-        if (b <= T) {
-            const double t = entry(add + (b < T ? dw[b] : surv), row[b], gam[b]);
-            if (t > neg_inf()) e = exp(t - shift);
-        }
-        double c = e;
-        for (int off = 1; off < 64; off <<= 1) {
-            const double dn = __shfl_up(c, off, 64);
-            if (lane >= off) c += dn;
-        }
-        c += base;
-        const unsigned long long pos = __ballot(e > 0.0), hit = __ballot(e > 0.0 && c > target);
-        if (hit) return __builtin_amdgcn_readfirstlane(b0 + __ffsll((long long)hit) - 1);
-        if (pos) last = b0 + 63 - __clzll((long long)pos);
-        base = __shfl(c, 63, 64);
-    }
-    return 0;
+    return wave_pick(lo, T, target, lane, base, last, [&](int b) {
+        const double t = entry(add + (b < T ? dw[b] : surv), row[b], gam[b]);
+        return t > neg_inf() ? exp(t - shift) : 0.0;
+    });
 }
 
 // frames [a, b) of a draw's row get state s: byte x by lane x mod 64, 64 consecutive bytes a store
@@ -229,14 +214,14 @@ int launch_dwelldraw_head(const DwelldrawParams &p, void *stream)
 {
     const int waves = kThreads / 64;
     hipLaunchKernelGGL(dwelldraw_head_kernel, dim3((unsigned)((p.n_traj + waves - 1) / waves)), dim3(kThreads), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launched();
 }
 
 int launch_dwelldraw(const DwelldrawParams &p, const DwelldrawParams *d_p, void *stream)
 {
     const int waves = kThreads / 64;
     hipLaunchKernelGGL(dwelldraw_kernel, dim3((unsigned)((p.n_draws + waves - 1) / waves)), dim3(kThreads), 0, (hipStream_t)stream, d_p);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launched();
 }
 
 } // namespace bild

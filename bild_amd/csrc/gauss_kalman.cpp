@@ -174,20 +174,20 @@ struct GaussKalCall {
 
         double *d_msd, *d_xv;
         int32_t *d_vidx, *d_midx, *d_rank, *d_iota;
-        SIM_TRY(bufs.put(&d_msd, m.msd.data(), m.msd.size()));
-        SIM_TRY(bufs.put(&d_vidx, vidx.data(), vidx.size()));
-        SIM_TRY(bufs.put(&d_midx, midx.data(), midx.size()));
-        SIM_TRY(bufs.put(&d_rank, rank.data(), rank.size()));
-        SIM_TRY(bufs.put(&d_xv, xv.data(), xv.size()));
+        BILD_TRY(bufs.put(&d_msd, m.msd.data(), m.msd.size()));
+        BILD_TRY(bufs.put(&d_vidx, vidx.data(), vidx.size()));
+        BILD_TRY(bufs.put(&d_midx, midx.data(), midx.size()));
+        BILD_TRY(bufs.put(&d_rank, rank.data(), rank.size()));
+        BILD_TRY(bufs.put(&d_xv, xv.data(), xv.size()));
         int nmax_shared = 0;
         for (int v : shared_n) nmax_shared = std::max(nmax_shared, v);
         std::vector<int32_t> iota(std::max(nmax_shared + 1, 1));
         for (size_t i = 0; i < iota.size(); ++i) iota[i] = (int32_t)i;
-        SIM_TRY(bufs.put(&d_iota, iota.data(), iota.size()));
+        BILD_TRY(bufs.put(&d_iota, iota.data(), iota.size()));
         std::vector<int64_t> shared_off((size_t)S * d + 1, 0);
         for (int sk = 0; sk < S * d; ++sk) shared_off[sk + 1] = shared_off[sk] + (int64_t)shared_n[sk] * shared_n[sk];
         double *d_shared;
-        SIM_TRY(bufs.put(&d_shared, nullptr, (size_t)shared_off[S * d]));
+        BILD_TRY(bufs.put(&d_shared, nullptr, (size_t)shared_off[S * d]));
 
         std::vector<GaussKalSet> sets(set_key.size());
         for (size_t e = 0; e < set_key.size(); ++e) {
@@ -224,17 +224,17 @@ struct GaussKalCall {
         }
         GaussSensSet *d_ssets;
         GaussSensJob *d_sjobs;
-        SIM_TRY(bufs.put(&d_ssets, ssets.data(), ssets.size()));
-        SIM_TRY(bufs.put(&d_sjobs, sjobs.data(), sjobs.size()));
-        SIM_TRY(bufs.put(&d_sets, sets.data(), sets.size()));
-        SIM_TRY(bufs.put(&d_refs, refs.data(), refs.size()));
-        SIM_TRY(bufs.put(&d_rec, nullptr, (size_t)rec_off[njobs]));
+        BILD_TRY(bufs.put(&d_ssets, ssets.data(), ssets.size()));
+        BILD_TRY(bufs.put(&d_sjobs, sjobs.data(), sjobs.size()));
+        BILD_TRY(bufs.put(&d_sets, sets.data(), sets.size()));
+        BILD_TRY(bufs.put(&d_refs, refs.data(), refs.size()));
+        BILD_TRY(bufs.put(&d_rec, nullptr, (size_t)rec_off[njobs]));
         // longest first, so that the long factorisations start early
         std::stable_sort(fact.begin(), fact.end(), [](const GaussKalJob &a, const GaussKalJob &b) { return a.n > b.n; });
         std::vector<GaussKalJob> all(solve);
         all.insert(all.end(), fact.begin(), fact.end());
         GaussKalJob *d_jobs;
-        SIM_TRY(bufs.put(&d_jobs, all.data(), all.size()));
+        BILD_TRY(bufs.put(&d_jobs, all.data(), all.size()));
         const int nso = (int)solve.size(), nfa = (int)fact.size();
         if (launch_gauss_sens_factor(d_ssets, d_sjobs, (int)sjobs.size(), 0, d_shared, nullptr, bufs.stream))
             return fail(BILD_ERR_HIP, "launch of the shared-factor kernel failed");
@@ -252,7 +252,7 @@ struct GaussKalCall {
                 c0 = c1;
             }
             double *d_scratch;
-            SIM_TRY(bufs.put(&d_scratch, nullptr, (size_t)widest));
+            BILD_TRY(bufs.put(&d_scratch, nullptr, (size_t)widest));
             for (int c0 = 0; c0 < nfa;) {
                 const int c1 = sim_chunk_end(slot_off, c0, nfa, budget);
                 for (int q = c0; q < c1; ++q) all[nso + q].fac = slot_off[q] - slot_off[c0];
@@ -307,17 +307,17 @@ extern "C" int bild_gauss_kalman_segments(const bild_gauss_model *m, int n_traj,
     if (n == 0 || nout == 0) return BILD_OK;
 
     GaussKalCall call(*m);
-    SIM_TRY(call.plan(n_traj, T, x, n, K1, seg_start, seg_state, traj_id, out->T_max, scratch_bytes));
+    BILD_TRY(call.plan(n_traj, T, x, n, K1, seg_start, seg_state, traj_id, out->T_max, scratch_bytes));
     // chunks of whole candidates whose outputs fit the budget, at least one candidate
     const int64_t row = (int64_t)out->T_max * m->d;
     const int64_t per = std::max<int64_t>(1, budget_doubles(scratch_bytes) / std::max<int64_t>(1, nout * row));
     const int64_t cmax = std::min<int64_t>(n, per);
     double *d_out[kKalOutputs] = {};
     for (int w = 0; w < kKalOutputs; ++w)
-        if (host_out[w]) SIM_TRY(call.bufs.put(&d_out[w], nullptr, (size_t)(cmax * row)));
+        if (host_out[w]) BILD_TRY(call.bufs.put(&d_out[w], nullptr, (size_t)(cmax * row)));
     for (int64_t c0 = 0; c0 < n; c0 += cmax) {
         const int64_t c1 = std::min(n, c0 + cmax);
-        SIM_TRY(call.scatter(c0, c1, d_out));
+        BILD_TRY(call.scatter(c0, c1, d_out));
         for (int w = 0; w < kKalOutputs; ++w)
             if (host_out[w])
                 HIP_TRY(hipMemcpyAsync(host_out[w] + c0 * row, d_out[w], (size_t)((c1 - c0) * row) * 8, hipMemcpyDeviceToHost, call.bufs.stream));
@@ -394,7 +394,7 @@ extern "C" int bild_gauss_kalman_mixture(const bild_gauss_model *m, int n_traj, 
     for (int64_t q = 0; q < nsel; ++q) gather(nref + q, order[q], traj_id ? traj_id[order[q]] : 0);
 
     GaussKalCall call(*m);
-    SIM_TRY(call.plan(n_traj, T, x, nref + nsel, K1, g_start.data(), g_state.data(), g_tid.data(), Tout, scratch_bytes));
+    BILD_TRY(call.plan(n_traj, T, x, nref + nsel, K1, g_start.data(), g_state.data(), g_tid.data(), Tout, scratch_bytes));
     // chunks of whole blocks (smoothed mean and variance of their candidates, the blocks' partial sums), at least one block
     const int64_t budget = budget_doubles(scratch_bytes);
     std::vector<int> bcut{0};
@@ -415,22 +415,22 @@ extern "C" int bild_gauss_kalman_mixture(const bild_gauss_model *m, int n_traj, 
     }
     int32_t *d_ref_row, *d_blk_traj, *d_blk_T, *d_run_b0, *d_lstart;
     double *d_ref, *d_w, *d_mean, *d_var, *d_part, *d_acc;
-    SIM_TRY(call.bufs.put(&d_ref_row, ref_row.data(), ref_row.size()));
-    SIM_TRY(call.bufs.put(&d_w, wts.data(), wts.size()));
-    SIM_TRY(call.bufs.put(&d_blk_traj, blk_traj.data(), blk_traj.size()));
-    SIM_TRY(call.bufs.put(&d_blk_T, blk_T.data(), blk_T.size()));
-    SIM_TRY(call.bufs.put(&d_run_b0, nullptr, (size_t)blk_max + 1));
-    SIM_TRY(call.bufs.put(&d_lstart, nullptr, (size_t)blk_max + 1));
-    SIM_TRY(call.bufs.put(&d_ref, nullptr, (size_t)(nref * row)));
-    SIM_TRY(call.bufs.put(&d_mean, nullptr, (size_t)(cand_max * row)));
-    SIM_TRY(call.bufs.put(&d_var, nullptr, (size_t)(cand_max * row)));
-    SIM_TRY(call.bufs.put(&d_part, nullptr, (size_t)(blk_max * row * 3)));
-    SIM_TRY(call.bufs.put(&d_acc, nullptr, (size_t)(nt * row * 3)));
+    BILD_TRY(call.bufs.put(&d_ref_row, ref_row.data(), ref_row.size()));
+    BILD_TRY(call.bufs.put(&d_w, wts.data(), wts.size()));
+    BILD_TRY(call.bufs.put(&d_blk_traj, blk_traj.data(), blk_traj.size()));
+    BILD_TRY(call.bufs.put(&d_blk_T, blk_T.data(), blk_T.size()));
+    BILD_TRY(call.bufs.put(&d_run_b0, nullptr, (size_t)blk_max + 1));
+    BILD_TRY(call.bufs.put(&d_lstart, nullptr, (size_t)blk_max + 1));
+    BILD_TRY(call.bufs.put(&d_ref, nullptr, (size_t)(nref * row)));
+    BILD_TRY(call.bufs.put(&d_mean, nullptr, (size_t)(cand_max * row)));
+    BILD_TRY(call.bufs.put(&d_var, nullptr, (size_t)(cand_max * row)));
+    BILD_TRY(call.bufs.put(&d_part, nullptr, (size_t)(blk_max * row * 3)));
+    BILD_TRY(call.bufs.put(&d_acc, nullptr, (size_t)(nt * row * 3)));
     HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)(nt * row * 3) * 8, call.bufs.stream));
     {
         double *o[kKalOutputs] = {};
         o[5] = d_ref;
-        SIM_TRY(call.scatter(0, nref, o));
+        BILD_TRY(call.scatter(0, nref, o));
     }
     std::vector<int32_t> run_b0, lstart;
     for (size_t c = 0; c + 1 < bcut.size(); ++c) {
@@ -438,7 +438,7 @@ extern "C" int bild_gauss_kalman_mixture(const bild_gauss_model *m, int n_traj, 
         double *o[kKalOutputs] = {};
         o[5] = d_mean;
         o[6] = d_var;
-        SIM_TRY(call.scatter(nref + blk_start[b0], nref + blk_start[b1], o));
+        BILD_TRY(call.scatter(nref + blk_start[b0], nref + blk_start[b1], o));
         run_b0.clear();
         for (int b = b0; b < b1; ++b)
             if (b == b0 || blk_traj[b] != blk_traj[b - 1]) run_b0.push_back(b - b0);

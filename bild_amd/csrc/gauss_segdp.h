@@ -17,6 +17,8 @@
 #pragma once
 #include <stdint.h>
 
+#include <vector>
+
 #include "gauss.h"
 
 namespace bild {
@@ -59,5 +61,33 @@ int launch_segdp_bmix(const SegdpParams &p, int m, void *stream);       // gamma
 int launch_segdp_backtrack(const SegdpParams &p, void *stream);
 int launch_segdp_cover(const SegdpParams &p, void *stream);
 int launch_segdp_carry(const SegdpParams &p, void *stream);
+
+// ---- the host side that the calls on the recursion share (gauss_segdp.cpp; evidence, draws, sensitivities) ----
+struct CallFrame;
+
+// transitions: not NULL, entries 0 or 1 (exact.cpp as well).  A BILD_* code.
+int segdp_check_transitions(int S, const uint8_t *transitions);
+// What every call on the recursion refuses, in this order: k_max outside 0 .. kSegdpMaxK, flags other than BILD_SEGDP_NAN_OMIT,
+// the transitions, a negative scratch_bytes, T_max shorter than a trajectory.  A BILD_* code.
+int segdp_check_call(int S, int k_max, unsigned flags, const uint8_t *transitions, int64_t scratch_bytes, int n_traj, const int *T,
+                     int T_max);
+
+// C(n, k) from exact integer steps (each division is exact), carried in a 64-bit mantissa once it no longer fits 128 bits
+long double binom_ld(int n, int k);
+// valid traces of k switches for every k < K: the sum of the entries of transitions^k
+std::vector<long double> trace_counts(int S, const uint8_t *tr, int K);
+int alloc_fwd(CallFrame &call, SegdpFwd *t, size_t n);
+
+// The profiles of one (trajectory, k) from the S x 5 block `fin` of the last column of the forward table; n_all = all
+// profiles of that k, omit = BILD_SEGDP_NAN_OMIT.  logev = top + log(z) - log(count); z = 0 where logev is -inf or NaN.
+struct SegdpEvidence {
+    double logev, kl, count, bad, top, z, map_logl;     // map_logl: NaN where no profile has one
+    bool any, usable;                                   // any profile at all; logev is a number
+};
+SegdpEvidence segdp_evidence(const double *fin, int S, long double n_all, bool omit);
+
+// the launches of one chunk: init, then mix and level per j, then the back-pointer walk / init, then blevel and bmix per level
+int segdp_run_forward(const SegdpParams &p, int k_max, void *stream);
+int segdp_run_backward(const SegdpParams &p, int k_max, void *stream);
 
 } // namespace bild

@@ -16,24 +16,22 @@
 //     a <= t < b.  A wave owns 64 frames t = b - 1 of one (trajectory, k, s) and walks the rows a: a suffix sum across the
 //     lanes gives each t the row's terms with b > t inside the tile, and the row's total goes to row_tot.  The carry kernel
 //     adds, per t, the totals of the tiles to the right over the rows a <= t.  Sums of non-negative terms only.
+// The reductions and scans across a wave and the carry's body are those of wave.h, which gauss_dwell.hip uses too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gauss_segdp.h"
+#include "wave.h"
 
 namespace bild {
 namespace {
 
 constexpr int kThreads = kSegdpThreads;
 
-__device__ __forceinline__ double neg_inf() { return __longlong_as_double(0xfff0000000000000ll); }
-
 __device__ __forceinline__ int64_t at(const SegdpParams &p, int traj, int level, int s, int b)
 {
     return (int64_t)traj * p.slot + ((int64_t)level * p.S + s) * p.ld + b;
 }
-
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) { return __shfl_xor(v, mask, 64); }
 
 __global__ void __launch_bounds__(kThreads) segdp_init_kernel(SegdpParams p, int backward)
 {
@@ -209,7 +207,7 @@ __global__ void __launch_bounds__(kThreads) segdp_blevel_kernel(SegdpParams p, i
             const double t = gM[b] + W[b];      // NaN compares false
             if (t > best) best = t;
         }
-        for (int off = 32; off >= 1; off >>= 1) best = fmax(best, shfl_xor_f64(best, off));   // no NaN among them
+        best = wave_max(best);
         if (best > neg_inf()) {
             for (int b = a + 1 + lane; b <= T; b += 64) {
                 const double gz = gZ[b];
@@ -218,7 +216,7 @@ __global__ void __launch_bounds__(kThreads) segdp_blevel_kernel(SegdpParams p, i
                 if (w != w) continue;
                 z += gz * exp(gM[b] + w - best);
             }
-            for (int off = 32; off >= 1; off >>= 1) z += shfl_xor_f64(z, off);
+            z = wave_sum(z);
         }
     }
     if (lane == 0) {
@@ -314,7 +312,7 @@ __global__ void __launch_bounds__(kThreads) segdp_cover_kernel(SegdpParams p)
     const int t = tile * kSegdpTile + lane, b = t + 1;
     if (tile * kSegdpTile >= T) return;     // the whole wave
     const double top = segdp_top(p, traj, k, T);
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = quiet_nan();
     const bool mine = b <= T;
     const double *__restrict__ W = td.W + (int64_t)s * td.w_per_state;
     double *__restrict__ row_tot = p.row_tot + ((((int64_t)traj * p.K + k) * p.S + s) * p.ntile + tile) * p.Tm;
@@ -344,11 +342,7 @@ __global__ void __launch_bounds__(kThreads) segdp_cover_kernel(SegdpParams p)
                     }
                 }
             }
-            // suffix sum across the lanes: lane l gets the terms of lanes >= l
-            for (int off = 1; off < 64; off <<= 1) {
-                const double up = __shfl_down(qv, off, 64);
-                if (lane + off < 64) qv += up;
-            }
+            qv = wave_scan_down(qv, lane);
             if (t >= a) acc += qv;
             if (lane == 0) row_tot[a] = qv;
         }
@@ -356,7 +350,7 @@ __global__ void __launch_bounds__(kThreads) segdp_cover_kernel(SegdpParams p)
     if (mine) p.cover[at(p, traj, k, s, t)] = acc;
 }
 
-// post(t) = cover(t) + sum over the rows a <= t of the totals of the tiles to the right of t's: one wave per (k, s, tile)
+// post from cover and the row totals (wave_carry): one wave per (k, s, tile)
 __global__ void __launch_bounds__(kThreads) segdp_carry_kernel(SegdpParams p)
 {
     const int traj = blockIdx.z;
@@ -365,33 +359,12 @@ __global__ void __launch_bounds__(kThreads) segdp_carry_kernel(SegdpParams p)
     const int lane = threadIdx.x & 63;
     const int tile = (int)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
     if (tile * kSegdpTile >= T) return;
-    const int t = tile * kSegdpTile + lane;
-    const int ntile = (T + kSegdpTile - 1) / kSegdpTile;
     const double *__restrict__ row_tot = p.row_tot + (((int64_t)traj * p.K + k) * p.S + s) * p.ntile * p.Tm;
-    double carry = 0.0;
-    const bool live = segdp_top(p, traj, k, T) > neg_inf();
-    for (int blk = 0; live && blk <= tile; ++blk) {
-        const int a = blk * kSegdpTile + lane;
-        double v = 0.0;
-        if (a < T)
-            for (int r = tile + 1; r < ntile; ++r) v += row_tot[(int64_t)r * p.Tm + a];
-        if (blk < tile) {
-            for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_f64(v, off);
-        } else {
-            // rows of the tile itself: row a counts for the frames t >= a
-            for (int off = 1; off < 64; off <<= 1) {
-                const double dn = __shfl_up(v, off, 64);
-                if (lane >= off) v += dn;
-            }
-        }
-        carry += v;
-    }
-    if (t < T) p.post[at(p, traj, k, s, t)] = p.cover[at(p, traj, k, s, t)] + carry;
+    const int64_t row = at(p, traj, k, s, 0);
+    wave_carry(row_tot, p.cover + row, p.post + row, T, p.Tm, tile, segdp_top(p, traj, k, T) > neg_inf(), lane);
 }
 
 } // namespace
-
-static int launched() { return hipGetLastError() == hipSuccess ? 0 : 1; }
 
 int launch_segdp_init(const SegdpParams &p, bool backward, void *stream)
 {

@@ -9,19 +9,19 @@
 //     exceeds u times the list's total.  The wave stops at the first block that reaches it.  The total is the table's own
 //     value (beta_m(t_i, s_i), or the head's Z), summed in another order than the scan: where rounding carries the target
 //     past the scan's end, the last entry of positive weight is taken.  A lane of weight 0 never qualifies.  The picks of a
-//     state run over S values and are done by every lane alike.
+//     state run over S values and are done by every lane alike.  The walk of a pick over the blocks is wave.h's wave_pick,
+//     as in gauss_dwelldraw.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gauss_segdraw.h"
 #include "philox.h"
+#include "wave.h"
 
 namespace bild {
 namespace {
 
 constexpr int kThreads = kSegdrawThreads;
-
-__device__ __forceinline__ double neg_inf() { return __longlong_as_double(0xfff0000000000000ll); }
 
 __device__ __forceinline__ int64_t at(const SegdrawParams &p, int traj, int level, int s, int b)
 {
@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(kThreads) segdraw_head_kernel(SegdrawParams p)
             if (t > best) best = t;
         }
     }
-    for (int off = 32; off >= 1; off >>= 1) best = fmax(best, __shfl_xor(best, off, 64));     // no NaN among them
+    best = wave_max(best);
     if (best > neg_inf()) {
         for (int s = 0; s < p.S; ++s) {
             const int64_t base = at(p, traj, k, s, 0);
@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(kThreads) segdraw_head_kernel(SegdrawParams p)
                 z += gz * exp(gM[b] + f - best);
             }
         }
-        for (int off = 32; off >= 1; off >>= 1) z += __shfl_xor(z, off, 64);
+        z = wave_sum(z);
     }
     if (lane == 0) {
         p.head[((int64_t)traj * p.K + k) * 2] = best;
@@ -73,25 +73,10 @@ __global__ void __launch_bounds__(kThreads) segdraw_head_kernel(SegdrawParams p)
 __device__ __forceinline__ int segdraw_pick(const double *__restrict__ row, const double *__restrict__ gM, const double *__restrict__ gZ, int lo,
                                             int hi, double M, double target, int lane, double &base, int &last)
 {
-    for (int b0 = lo; b0 <= hi; b0 += 64) {
-        const int b = b0 + lane;
-        double e = 0.0;
-        if (b <= hi) {
-            const double gz = gZ[b], w = row[b];
-            if (gz > 0.0 && w == w) e = gz * exp(gM[b] + w - M);
-        }
-        double c = e;
-        for (int off = 1; off < 64; off <<= 1) {
-            const double dn = __shfl_up(c, off, 64);
-            if (lane >= off) c += dn;
-        }
-        c += base;
-        const unsigned long long pos = __ballot(e > 0.0), hit = __ballot(e > 0.0 && c > target);
-        if (hit) return __builtin_amdgcn_readfirstlane(b0 + __ffsll((long long)hit) - 1);
-        if (pos) last = b0 + 63 - __clzll((long long)pos);
-        base = __shfl(c, 63, 64);
-    }
-    return 0;
+    return wave_pick(lo, hi, target, lane, base, last, [&](int b) {
+        const double gz = gZ[b], w = row[b];
+        return gz > 0.0 && w == w ? gz * exp(gM[b] + w - M) : 0.0;
+    });
 }
 
 // (The parameter block is read from device memory where a value is needed: passed as kernel arguments, all of it is held in
@@ -193,7 +178,7 @@ __global__ void __launch_bounds__(kThreads) segdraw_kernel(const SegdrawParams *
         p.logl[r] = acc;
     } else {
         for (int j = 0; j < K; ++j) p.seg_start[seg0 + j] = -1, p.seg_state[seg0 + j] = -1;
-        p.logl[r] = __longlong_as_double(0x7ff8000000000000ll);
+        p.logl[r] = quiet_nan();
         for (int j = 0; p.uniforms_out && j < U; ++j) p.uniforms_out[u0 + j] = 0.0;
     }
 }
@@ -205,14 +190,14 @@ int launch_segdraw_head(const SegdrawParams &p, void *stream)
     const int waves = kThreads / 64;
     const dim3 grid((unsigned)((p.K + waves - 1) / waves), (unsigned)p.n_traj);
     hipLaunchKernelGGL(segdraw_head_kernel, grid, dim3(kThreads), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launched();
 }
 
 int launch_segdraw(const SegdrawParams &p, const SegdrawParams *d_p, void *stream)
 {
     const int waves = kThreads / 64;
     hipLaunchKernelGGL(segdraw_kernel, dim3((unsigned)((p.n_draws + waves - 1) / waves)), dim3(kThreads), 0, (hipStream_t)stream, d_p);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launched();
 }
 
 } // namespace bild

@@ -1,91 +1,15 @@
 // Gradient of the exact evidence of GenericGaussianModel (include/bild_amd.h, "evidence sensitivities"; DESIGN.md section
-// 20): the refusals, the chunks of whole trajectories, the segment recursion's launches (gauss_segdp.hip, as they are), the
-// host's formulas on the last column of the forward table (those of gauss_segdp.cpp, so that logev is the same number),
-// the weight table and the weighted tangent jobs.  Kernels: gauss_segsens.hip.
+// 20): the refusals, the chunks of whole trajectories, the segment recursion's launches and its formulas on the last column
+// of the forward table (gauss_segdp.h: the functions gauss_segdp.cpp calls, so that logev is the same number), the weight
+// table and the weighted tangent jobs.  Kernels: gauss_segsens.hip.
 #include <algorithm>
 #include <cmath>
 #include <limits>
 
+#include "gauss_call.h"
 #include "gauss_segsens.h"
 #include "gauss_windows.h"
-#include "internal.h"
-#include "likelihood.h"
 #include "sim_host.h"
-
-namespace {
-
-using namespace bild;
-
-#define SS_TRY(x)                       \
-    do {                                \
-        int rc_ = (x);                  \
-        if (rc_ != BILD_OK) return rc_; \
-    } while (0)
-
-// Device memory of one call, freed on every path
-struct Bufs {
-    std::vector<void *> ptrs;
-    ~Bufs()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class X> int alloc(X **out, size_t count)
-    {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(X));
-        if (e != hipSuccess) return fail(BILD_ERR_NOMEM, "hipMalloc(%zu) failed: %s", count * sizeof(X), hipGetErrorString(e));
-        ptrs.push_back(p);
-        *out = static_cast<X *>(p);
-        return BILD_OK;
-    }
-};
-
-// C(n, k) and the valid traces of k switches: gauss_segdp.cpp's, operation for operation
-long double binom_ld(int n, int k)
-{
-    if (k < 0 || n < k) return 0.0L;
-    unsigned __int128 c = 1;
-    for (int i = 0; i < k; ++i) {
-        const unsigned __int128 f = (unsigned __int128)(n - i);
-        if (c >> 100) {
-            long double d = (long double)c;
-            for (int i2 = i; i2 < k; ++i2) d = d * (long double)(n - i2) / (long double)(i2 + 1);
-            return d;
-        }
-        c = c * f / (unsigned __int128)(i + 1);
-    }
-    return (long double)c;
-}
-
-std::vector<long double> trace_counts(int S, const uint8_t *tr, int K)
-{
-    std::vector<long double> out(K), v(S, 1.0L), w(S);
-    for (int k = 0; k < K; ++k) {
-        long double n = 0.0L;
-        for (long double x : v) n += x;
-        out[k] = n;
-        for (int a = 0; a < S; ++a) {
-            long double acc = 0.0L;
-            for (int b = 0; b < S; ++b)
-                if (tr[a * S + b]) acc += v[b];
-            w[a] = acc;
-        }
-        v.swap(w);
-    }
-    return out;
-}
-
-int alloc_fwd(Bufs &bufs, SegdpFwd *t, size_t n)
-{
-    SS_TRY(bufs.alloc(&t->M, n));
-    SS_TRY(bufs.alloc(&t->Z, n));
-    SS_TRY(bufs.alloc(&t->R, n));
-    SS_TRY(bufs.alloc(&t->ok, n));
-    SS_TRY(bufs.alloc(&t->bad, n));
-    return bufs.alloc(&t->arg, n);
-}
-
-} // namespace
 
 extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const bild_gauss_trajset *ts, const double *x, int k_max,
                                                 const uint8_t *transitions, unsigned flags, const double *log_k_prior, int P,
@@ -93,18 +17,13 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
 {
     int n_traj = 0;
     const int *T = nullptr;
-    SS_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
+    BILD_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
     if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
-    if (k_max < 0 || k_max > kSegdpMaxK)
-        return fail(BILD_ERR_UNSUPPORTED, "k_max = %d: the segment recursion supports 0 <= k_max <= %d", k_max, kSegdpMaxK);
-    if (flags & ~BILD_SEGDP_NAN_OMIT) return fail(BILD_ERR_INVALID, "flags = %u: unknown bits", flags);
     const int S = m->S, d = m->d, L1 = m->L + 1;
-    if (!transitions) return fail(BILD_ERR_INVALID, "transitions is NULL");
-    for (int i = 0; i < S * S; ++i)
-        if (transitions[i] > 1) return fail(BILD_ERR_INVALID, "transitions[%d] = %d; must be 0 or 1", i, transitions[i]);
-    if (scratch_bytes < 0) return fail(BILD_ERR_INVALID, "scratch_bytes = %lld is negative", (long long)scratch_bytes);
+    // (nothing here is padded to a T_max, so no trajectory is too long for it)
+    BILD_TRY(segdp_check_call(S, k_max, flags, transitions, scratch_bytes, n_traj, T, std::numeric_limits<int>::max()));
     if (n_traj == 0) return BILD_OK;
-    SS_TRY(gauss_check_args(m, n_traj, T, x, 0, 1, nullptr, nullptr, nullptr, P, dm));
+    BILD_TRY(gauss_check_args(m, n_traj, T, x, 0, 1, nullptr, nullptr, nullptr, P, dm));
     const int K = k_max + 1;
     if (log_k_prior)
         for (int j = 0; j < n_traj; ++j) {
@@ -183,42 +102,32 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
                 for (int r = 0; r < V; ++r) add(r, false);
             }
 
-    const GaussTraj *d_trajs = nullptr;
-    void *stream = nullptr;
-    std::mutex *mu = nullptr;
-    SS_TRY(internal_gauss_set_device(m, ts, &d_trajs, &stream, &mu));
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(*mu);      // the set's stream: one call at a time
+    CallFrame call;
+    BILD_TRY(call.open(m, ts));
+    hipStream_t st = call.st;
 
-    // chunks of whole trajectories within the budget (at least one): the recursion's tables and the weight table
+    // a trajectory's share of the chunk: the recursion's tables and the weight table
     const int64_t per_traj = slot * (2 * (5 * 8 + 4) + 4 * 8) + om_slot * 8 + (int64_t)K * K * 8 + (int64_t)K * S * 40 + (int64_t)K * 16;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const int64_t budget = sim_scratch_bytes(scratch_bytes, free_b);
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(budget / per_traj, n_traj));
+    int chunk = 0;
+    BILD_TRY(call.chunk_of(per_traj, scratch_bytes, n_traj, &chunk));
 
-    Bufs bufs;
-    struct Drain {      // (declared after the buffers: on an error path the stream is drained before they are freed)
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{st};
     SegdpParams p{};
     SegsensWeights w{};
     uint8_t *d_tr = nullptr;
     double *d_coef = nullptr, *d_top = nullptr;
-    SS_TRY(bufs.alloc(&d_tr, (size_t)S * S));
-    SS_TRY(alloc_fwd(bufs, &p.A, (size_t)chunk * slot));
-    SS_TRY(alloc_fwd(bufs, &p.alpha, (size_t)chunk * slot));
-    SS_TRY(bufs.alloc(&p.map_seg_start, (size_t)chunk * K * K));
-    SS_TRY(bufs.alloc(&p.map_seg_state, (size_t)chunk * K * K));
-    SS_TRY(bufs.alloc(&p.fin, (size_t)chunk * K * S * 5));
-    SS_TRY(bufs.alloc(&p.beta.M, (size_t)chunk * slot));
-    SS_TRY(bufs.alloc(&p.beta.Z, (size_t)chunk * slot));
-    SS_TRY(bufs.alloc(&p.gamma.M, (size_t)chunk * slot));
-    SS_TRY(bufs.alloc(&p.gamma.Z, (size_t)chunk * slot));
-    SS_TRY(bufs.alloc(&w.omega, (size_t)chunk * om_slot));
-    SS_TRY(bufs.alloc(&d_coef, (size_t)chunk * K));
-    SS_TRY(bufs.alloc(&d_top, (size_t)chunk * K));
+    BILD_TRY(call.alloc(&d_tr, (size_t)S * S));
+    BILD_TRY(alloc_fwd(call, &p.A, (size_t)chunk * slot));
+    BILD_TRY(alloc_fwd(call, &p.alpha, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.map_seg_start, (size_t)chunk * K * K));
+    BILD_TRY(call.alloc(&p.map_seg_state, (size_t)chunk * K * K));
+    BILD_TRY(call.alloc(&p.fin, (size_t)chunk * K * S * 5));
+    BILD_TRY(call.alloc(&p.beta.M, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.beta.Z, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.gamma.M, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&p.gamma.Z, (size_t)chunk * slot));
+    BILD_TRY(call.alloc(&w.omega, (size_t)chunk * om_slot));
+    BILD_TRY(call.alloc(&d_coef, (size_t)chunk * K));
+    BILD_TRY(call.alloc(&d_top, (size_t)chunk * K));
     HIP_TRY(hipMemcpyAsync(d_tr, transitions, (size_t)S * S, hipMemcpyHostToDevice, st));
     p.tr = d_tr;
     p.slot = slot;
@@ -247,12 +156,12 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
     for (int sk = 0; sk < S * d; ++sk) shared_off[sk + 1] = shared_off[sk] + (int64_t)Pf * Wf * shared_n[sk] * shared_n[sk];
     double *d_msd, *d_dmsd, *d_xv, *d_shared;
     int32_t *d_vidx, *d_iota;
-    SS_TRY(bufs.alloc(&d_msd, m->msd.size()));
-    SS_TRY(bufs.alloc(&d_dmsd, dmsd.size()));
-    SS_TRY(bufs.alloc(&d_vidx, vidx.size()));
-    SS_TRY(bufs.alloc(&d_xv, xv.size()));
-    SS_TRY(bufs.alloc(&d_iota, iota.size()));
-    SS_TRY(bufs.alloc(&d_shared, (size_t)shared_off[S * d]));
+    BILD_TRY(call.alloc(&d_msd, m->msd.size()));
+    BILD_TRY(call.alloc(&d_dmsd, dmsd.size()));
+    BILD_TRY(call.alloc(&d_vidx, vidx.size()));
+    BILD_TRY(call.alloc(&d_xv, xv.size()));
+    BILD_TRY(call.alloc(&d_iota, iota.size()));
+    BILD_TRY(call.alloc(&d_shared, (size_t)shared_off[S * d]));
     HIP_TRY(hipMemcpyAsync(d_msd, m->msd.data(), m->msd.size() * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_dmsd, dmsd.data(), dmsd.size() * 8, hipMemcpyHostToDevice, st));
     if (!vidx.empty()) {
@@ -301,8 +210,8 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
         }
     GaussSensSet *d_sets;
     GaussSensJob *d_shared_jobs;
-    SS_TRY(bufs.alloc(&d_sets, sets.size()));
-    SS_TRY(bufs.alloc(&d_shared_jobs, shared_jobs.size()));
+    BILD_TRY(call.alloc(&d_sets, sets.size()));
+    BILD_TRY(call.alloc(&d_shared_jobs, shared_jobs.size()));
     HIP_TRY(hipMemcpyAsync(d_sets, sets.data(), sets.size() * sizeof(GaussSensSet), hipMemcpyHostToDevice, st));
     if (!shared_jobs.empty())
         HIP_TRY(hipMemcpyAsync(d_shared_jobs, shared_jobs.data(), shared_jobs.size() * sizeof(GaussSensJob), hipMemcpyHostToDevice, st));
@@ -319,10 +228,10 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
     }
     SegsensJob *d_jobs;
     double *d_out, *d_scratch = nullptr;
-    SS_TRY(bufs.alloc(&d_jobs, max_jobs));
-    SS_TRY(bufs.alloc(&d_out, max_jobs * kGaussSensStride));
+    BILD_TRY(call.alloc(&d_jobs, max_jobs));
+    BILD_TRY(call.alloc(&d_out, max_jobs * kGaussSensStride));
     int64_t scratch_cap = 0;
-    const int64_t fact_budget = budget / 8;
+    const int64_t fact_budget = call.budget / 8;
 
     const std::vector<long double> ntraces = trace_counts(S, transitions, K);
     std::vector<double> fin((size_t)chunk * K * S * 5), coef((size_t)chunk * K), top((size_t)chunk * K), h_out(max_jobs * kGaussSensStride);
@@ -333,51 +242,26 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
 
     for (int j0 = 0; j0 < n_traj; j0 += chunk) {
         const int nc = std::min(chunk, n_traj - j0);
-        p.trajs = d_trajs + j0;
+        p.trajs = call.d_trajs + j0;
         p.n_traj = nc;
-        if (launch_segdp_init(p, false, st)) return fail(BILD_ERR_HIP, "launch of the segment recursion's first level failed");
-        for (int j = 1; j <= k_max; ++j)
-            if (launch_segdp_mix(p, j, st) || launch_segdp_level(p, j, st))
-                return fail(BILD_ERR_HIP, "launch of level %d of the segment recursion failed", j);
-        if (launch_segdp_backtrack(p, st)) return fail(BILD_ERR_HIP, "launch of the back-pointer walk failed");
-        if (launch_segdp_init(p, true, st)) return fail(BILD_ERR_HIP, "launch of the backward recursion's first level failed");
-        for (int lv = 0; lv < k_max; ++lv)
-            if (launch_segdp_blevel(p, lv, st) || launch_segdp_bmix(p, lv + 1, st))
-                return fail(BILD_ERR_HIP, "launch of level %d of the backward recursion failed", lv);
+        BILD_TRY(segdp_run_forward(p, k_max, st));
+        BILD_TRY(segdp_run_backward(p, k_max, st));
         HIP_TRY(hipMemcpyAsync(fin.data(), p.fin, (size_t)nc * K * S * 5 * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
 
-        // logev of every k (gauss_segdp.cpp's formulas), the posterior over k, and the scale of every k's weights
+        // logev of every k (segdp_evidence), the posterior over k, and the scale of every k's weights
         for (int i = 0; i < nc; ++i) {
             const int jt = j0 + i, Tj = T[jt];
             std::vector<double> logev(K), zk(K), lw(K);
             bool bad_traj = false;
             double lmax = ninf;
             for (int k = 0; k < K; ++k) {
-                const double *f = fin.data() + ((size_t)i * K + k) * S * 5;
-                const long double n_all = binom_ld(Tj - 1, k) * ntraces[k];
-                double ok = 0.0, bad = 0.0, tp = ninf;
-                for (int s = 0; s < S; ++s) {
-                    ok += f[s * 5 + 3];
-                    bad += f[s * 5 + 4];
-                    if (f[s * 5 + 1] > 0.0) tp = std::max(tp, f[s * 5]);
-                }
-                const bool any = n_all > 0.0L;
-                const double count = !any ? 0.0 : omit ? ok : (double)n_all;
-                const double log_count = omit ? std::log(ok) : (double)logl(n_all);
-                double le = ninf, z = 0.0;
-                if (any && !omit && bad > 0.0) le = nan;
-                else if (any && count > 0.0 && tp != ninf) {
-                    for (int s = 0; s < S; ++s) {
-                        if (!(f[s * 5 + 1] > 0.0)) continue;
-                        const double wgt = f[s * 5 + 1] * std::exp(f[s * 5] - tp);
-                        z += wgt;
-                    }
-                    le = tp + std::log(z) - log_count;
-                }
+                const SegdpEvidence e =
+                    segdp_evidence(fin.data() + ((size_t)i * K + k) * S * 5, S, binom_ld(Tj - 1, k) * ntraces[k], omit);
+                const double le = e.logev;
                 logev[k] = le;
-                zk[k] = z;
-                top[(size_t)i * K + k] = tp;
+                zk[k] = e.z;
+                top[(size_t)i * K + k] = e.top;
                 const double lp = log_k_prior ? log_k_prior[(size_t)jt * K + k] : 0.0;
                 lw[k] = lp > ninf ? lp + le : ninf;     // a k of prior weight 0 does not count, NaN or not
                 if (std::isnan(lw[k])) bad_traj = true;
@@ -439,7 +323,7 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
             c0 = c1;
         }
         if (widest > scratch_cap) {
-            SS_TRY(bufs.alloc(&d_scratch, (size_t)widest));
+            BILD_TRY(call.alloc(&d_scratch, (size_t)widest));
             scratch_cap = widest;
         }
         if (!all.empty()) HIP_TRY(hipMemcpyAsync(d_jobs, all.data(), all.size() * sizeof(SegsensJob), hipMemcpyHostToDevice, st));

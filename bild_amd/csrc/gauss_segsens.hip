@@ -18,14 +18,13 @@
 #include <stdint.h>
 
 #include "gauss_segsens.h"
+#include "wave.h"
 
 namespace bild {
 namespace {
 
 constexpr int kThreads = 256;
 constexpr double kHalfLog2Pi = 0.91893853320467274178;
-
-__device__ __forceinline__ double neg_inf() { return __longlong_as_double(0xfff0000000000000ll); }
 
 __device__ __forceinline__ int64_t at(const SegdpParams &p, int traj, int level, int s, int b)
 {
@@ -75,11 +74,7 @@ __global__ void __launch_bounds__(kThreads) segsens_weight_kernel(SegdpParams p,
                 qv += ck * acc;
             }
         }
-        // suffix sum across the lanes: lane l gets the terms of lanes >= l
-        for (int off = 1; off < 64; off <<= 1) {
-            const double up = __shfl_down(qv, off, 64);
-            if (lane + off < 64) qv += up;
-        }
+        qv = wave_scan_down(qv, lane);
         qv += carry;
         if (mine) dst[b] = qv;
         carry = __shfl(qv, 0, 64);
@@ -285,7 +280,7 @@ template <int P>
 int launch_factor(const GaussSensSet *sets, const SegsensJob *jobs, int njobs, const double *omega, double *base, double *out, void *stream)
 {
     hipLaunchKernelGGL(segsens_factor_kernel<P>, dim3(njobs), dim3(kThreads), 0, (hipStream_t)stream, sets, jobs, omega, base, out);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launched();
 }
 
 template <int P>
@@ -296,7 +291,7 @@ int launch_solve(const GaussSensSet *sets, const SegsensJob *jobs, int njobs, in
         hipSuccess)
         return 1;
     hipLaunchKernelGGL(segsens_solve_kernel<P>, dim3(njobs), dim3(kThreads), lds, (hipStream_t)stream, sets, jobs, nmax, omega, out);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launched();
 }
 
 } // namespace
@@ -306,7 +301,7 @@ int launch_segsens_weight(const SegdpParams &p, const SegsensWeights &w, void *s
     const int waves = kThreads / 64;
     const dim3 grid((unsigned)((p.Tm + waves - 1) / waves), (unsigned)p.S, (unsigned)p.n_traj);
     hipLaunchKernelGGL(segsens_weight_kernel, grid, dim3(kThreads), 0, (hipStream_t)stream, p, w);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
+    return launched();
 }
 
 int launch_segsens_factor(const GaussSensSet *sets, const SegsensJob *jobs, int njobs, int P, const double *omega, double *base, double *out,

@@ -153,18 +153,18 @@ extern "C" int bild_gauss_logl_sensitivities(const bild_gauss_model *m, int n_tr
     for (size_t i = 0; i < iota.size(); ++i) iota[i] = (int32_t)i;
     double *d_msd, *d_dmsd, *d_xv;
     int32_t *d_vidx, *d_iota;
-    SIM_TRY(bufs.put(&d_msd, m->msd.data(), m->msd.size()));
-    SIM_TRY(bufs.put(&d_dmsd, dmsd.data(), dmsd.size()));
-    SIM_TRY(bufs.put(&d_vidx, vidx.data(), vidx.size()));
-    SIM_TRY(bufs.put(&d_xv, xv.data(), xv.size()));
-    SIM_TRY(bufs.put(&d_iota, iota.data(), iota.size()));
+    BILD_TRY(bufs.put(&d_msd, m->msd.data(), m->msd.size()));
+    BILD_TRY(bufs.put(&d_dmsd, dmsd.data(), dmsd.size()));
+    BILD_TRY(bufs.put(&d_vidx, vidx.data(), vidx.size()));
+    BILD_TRY(bufs.put(&d_xv, xv.data(), xv.size()));
+    BILD_TRY(bufs.put(&d_iota, iota.data(), iota.size()));
 
     // shared factors: per (state, dimension) with gap-free jobs, P = 0: L (n^2); else Pf pairs (L, dL_q) interleaved (2 n^2)
     std::vector<int64_t> shared_off((size_t)S * d + 1, 0);
     const int W = P > 0 ? 2 : 1;
     for (int sk = 0; sk < S * d; ++sk) shared_off[sk + 1] = shared_off[sk] + (int64_t)Pf * W * shared_n[sk] * shared_n[sk];
     double *d_shared;
-    SIM_TRY(bufs.put(&d_shared, nullptr, (size_t)shared_off[S * d]));
+    BILD_TRY(bufs.put(&d_shared, nullptr, (size_t)shared_off[S * d]));
     auto fill_set = [&](GaussSensSet &e, int s, int k) {
         const int sk = s * d + k;
         e.msd = d_msd + (size_t)sk * L1;
@@ -207,14 +207,14 @@ extern "C" int bild_gauss_logl_sensitivities(const bild_gauss_model *m, int n_tr
     GaussSensSet *d_sets;
     GaussSensJob *d_jobs;
     double *d_out;
-    SIM_TRY(bufs.put(&d_sets, sets.data(), sets.size()));
+    BILD_TRY(bufs.put(&d_sets, sets.data(), sets.size()));
     // longest first, so that the long factorisations start early
     std::stable_sort(fact.begin(), fact.end(), [](const GaussSensJob &a, const GaussSensJob &b) { return a.n > b.n; });
     std::vector<GaussSensJob> all(shared_jobs);
     all.insert(all.end(), solve.begin(), solve.end());
     all.insert(all.end(), fact.begin(), fact.end());
-    SIM_TRY(bufs.put(&d_jobs, all.data(), all.size()));
-    SIM_TRY(bufs.put(&d_out, nullptr, (size_t)njobs * kGaussSensStride));
+    BILD_TRY(bufs.put(&d_jobs, all.data(), all.size()));
+    BILD_TRY(bufs.put(&d_out, nullptr, (size_t)njobs * kGaussSensStride));
     const int nsh = (int)shared_jobs.size(), nso = (int)solve.size(), nfa = (int)fact.size();
 
     if (launch_gauss_sens_factor(d_sets, d_jobs, nsh, P > 0 ? 1 : 0, d_shared, d_out, bufs.stream))
@@ -235,7 +235,7 @@ extern "C" int bild_gauss_logl_sensitivities(const bild_gauss_model *m, int n_tr
             c0 = c1;
         }
         double *d_scratch;
-        SIM_TRY(bufs.put(&d_scratch, nullptr, (size_t)widest));
+        BILD_TRY(bufs.put(&d_scratch, nullptr, (size_t)widest));
         for (int c0 = 0; c0 < nfa;) {
             const int c1 = sim_chunk_end(slot_off, c0, nfa, budget);
             for (int q = c0; q < c1; ++q) all[nsh + nso + q].fac = slot_off[q] - slot_off[c0];

@@ -34,8 +34,8 @@ int ensure_factors(const bild_gauss_model *m, int T, SimBufs &bufs)
     for (int t = 0; t < T; ++t) times[t] = t;
     double *d_msd;
     int32_t *d_times;
-    SIM_TRY(bufs.put(&d_msd, m->msd.data(), m->msd.size()));
-    SIM_TRY(bufs.put(&d_times, times.data(), times.size()));
+    BILD_TRY(bufs.put(&d_msd, m->msd.data(), m->msd.size()));
+    BILD_TRY(bufs.put(&d_times, times.data(), times.size()));
     std::vector<GaussJobSet> sets(sd);
     std::vector<GaussJob> jobs(sd);
     for (int i = 0; i < sd; ++i) {
@@ -50,8 +50,8 @@ int ensure_factors(const bild_gauss_model *m, int T, SimBufs &bufs)
     }
     GaussJobSet *d_sets;
     GaussJob *d_jobs;
-    SIM_TRY(bufs.put(&d_sets, sets.data(), sets.size()));
-    SIM_TRY(bufs.put(&d_jobs, jobs.data(), jobs.size()));
+    BILD_TRY(bufs.put(&d_sets, sets.data(), sets.size()));
+    BILD_TRY(bufs.put(&d_jobs, jobs.data(), jobs.size()));
     // (the cache owns the memory from here: a failure below leaves it allocated but empty, freed by the next build or destroy)
     m->factors = factors;
     if (launch_gauss_factor_sets(d_sets, d_jobs, sd, bufs.stream)) return fail(BILD_ERR_HIP, "launch of the factor kernel failed");
@@ -138,7 +138,7 @@ extern "C" int bild_gauss_simulate(const bild_gauss_model *m, int n, const int32
     std::lock_guard<std::mutex> lock(m->sim_mu);
     SimBufs bufs;
     HIP_TRY(hipStreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
-    SIM_TRY(ensure_factors(m, Tmax, bufs));
+    BILD_TRY(ensure_factors(m, Tmax, bufs));
 
     // the columns, chunk by chunk, in the loop's order of the normals: per trajectory, interval, dimension
     std::vector<GaussSimCol> cols;
@@ -211,20 +211,20 @@ extern "C" int bild_gauss_simulate(const bild_gauss_model *m, int n, const int32
     for (int sk = 0; sk < S * d; ++sk) Ls[sk] = m->factors + m->factor_off[sk];
     GaussSimProduct p{};
     GaussSimAssemble a{};
-    SIM_TRY(bufs.put(&p.cols, cols.data(), cols.size()));
-    SIM_TRY(bufs.put(&p.blocks, blocks.data(), blocks.size()));
-    SIM_TRY(bufs.put(&p.tasks, tasks.data(), tasks.size()));
+    BILD_TRY(bufs.put(&p.cols, cols.data(), cols.size()));
+    BILD_TRY(bufs.put(&p.blocks, blocks.data(), blocks.size()));
+    BILD_TRY(bufs.put(&p.tasks, tasks.data(), tasks.size()));
     double *d_z, *d_out;
-    SIM_TRY(bufs.put(&d_z, nullptr, (size_t)scratch_doubles));
-    SIM_TRY(bufs.put(&d_out, nullptr, (size_t)rows * d));
-    SIM_TRY(bufs.put(&a.frame_off, frame_off.data(), n + 1));
-    SIM_TRY(bufs.put(&a.iv_off, iv_off.data(), n + 1));
-    SIM_TRY(bufs.put(&a.iv, iv.data(), iv.size()));
-    SIM_TRY(bufs.put(&a.order, m->order.data(), m->order.size()));
-    SIM_TRY(bufs.put(&a.mean, m->mean.data(), m->mean.size()));
-    SIM_TRY(bufs.put(&a.L, Ls.data(), Ls.size()));
+    BILD_TRY(bufs.put(&d_z, nullptr, (size_t)scratch_doubles));
+    BILD_TRY(bufs.put(&d_out, nullptr, (size_t)rows * d));
+    BILD_TRY(bufs.put(&a.frame_off, frame_off.data(), n + 1));
+    BILD_TRY(bufs.put(&a.iv_off, iv_off.data(), n + 1));
+    BILD_TRY(bufs.put(&a.iv, iv.data(), iv.size()));
+    BILD_TRY(bufs.put(&a.order, m->order.data(), m->order.size()));
+    BILD_TRY(bufs.put(&a.mean, m->mean.data(), m->mean.size()));
+    BILD_TRY(bufs.put(&a.L, Ls.data(), Ls.size()));
     uint8_t *d_missing;
-    SIM_TRY(bufs.put(&d_missing, missing, rows));
+    BILD_TRY(bufs.put(&d_missing, missing, rows));
     if (!missing) HIP_TRY(hipMemsetAsync(d_missing, 0, rows, bufs.stream));
     a.missing = d_missing;
     a.out = p.out = d_out;

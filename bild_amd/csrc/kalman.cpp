@@ -87,13 +87,13 @@ struct KalCall {
                     G[((size_t)s * L + i) * d + k] = m.Gq[((size_t)s * n + i) * d + k];
                 }
             }
-        SIM_TRY(bufs.put(&p.lam, lam.data(), lam.size()));
-        SIM_TRY(bufs.put(&p.sig, sig.data(), sig.size()));
-        SIM_TRY(bufs.put(&p.wq, wq.data(), wq.size()));
-        SIM_TRY(bufs.put(&p.C0, C0.data(), C0.size()));
-        SIM_TRY(bufs.put(&p.Q, Q.data(), Q.size()));
-        SIM_TRY(bufs.put(&p.M0, M0.data(), M0.size()));
-        SIM_TRY(bufs.put(&p.G, G.data(), G.size()));
+        BILD_TRY(bufs.put(&p.lam, lam.data(), lam.size()));
+        BILD_TRY(bufs.put(&p.sig, sig.data(), sig.size()));
+        BILD_TRY(bufs.put(&p.wq, wq.data(), wq.size()));
+        BILD_TRY(bufs.put(&p.C0, C0.data(), C0.size()));
+        BILD_TRY(bufs.put(&p.Q, Q.data(), Q.size()));
+        BILD_TRY(bufs.put(&p.M0, M0.data(), M0.size()));
+        BILD_TRY(bufs.put(&p.G, G.data(), G.size()));
         // (the staging vectors go out of scope: the copies must have finished)
         HIP_TRY(hipStreamSynchronize(bufs.stream));
         p.trajs = ts.d_descs;
@@ -107,8 +107,8 @@ struct KalCall {
     int64_t rec_doubles(int j) const { return (int64_t)ts.descs[j].dstar * ts.descs[j].T * REC; }
     int reserve(int64_t rec_doubles_max, int64_t cand_max)
     {
-        SIM_TRY(bufs.put(&p.rec, nullptr, (size_t)std::max<int64_t>(rec_doubles_max, 1)));
-        SIM_TRY(bufs.put(&d_rec_off, nullptr, (size_t)std::max<int64_t>(cand_max * ts.dstar_max, 1)));
+        BILD_TRY(bufs.put(&p.rec, nullptr, (size_t)std::max<int64_t>(rec_doubles_max, 1)));
+        BILD_TRY(bufs.put(&d_rec_off, nullptr, (size_t)std::max<int64_t>(cand_max * ts.dstar_max, 1)));
         task_cap = cand_max * ts.dstar_max;
         rec_cap = rec_doubles_max;
         return BILD_OK;
@@ -171,7 +171,7 @@ extern "C" int bild_kalman_segments(const bild_model *m, const bild_trajset *ts,
     if (n == 0 || nout == 0) return BILD_OK;
 
     KalCall kc(*m, *ts);
-    SIM_TRY(kc.init(out->T_max));
+    BILD_TRY(kc.init(out->T_max));
     const int d = m->d;
     const int64_t row = (int64_t)out->T_max * d;
     // chunks of whole candidates: records + the wanted outputs within the budget, at least one candidate
@@ -190,17 +190,17 @@ extern "C" int bild_kalman_segments(const bild_model *m, const bild_trajset *ts,
         cand_max = std::max(cand_max, r + 1 - cut.back());
     }
     cut.push_back(n);
-    SIM_TRY(kc.reserve(rec_max, cand_max));
+    BILD_TRY(kc.reserve(rec_max, cand_max));
     int32_t *d_start, *d_state, *d_tid = nullptr;
-    SIM_TRY(kc.bufs.put(&d_start, seg_start, (size_t)n * K1));
-    SIM_TRY(kc.bufs.put(&d_state, seg_state, (size_t)n * K1));
-    if (traj_id) SIM_TRY(kc.bufs.put(&d_tid, traj_id, (size_t)n));
+    BILD_TRY(kc.bufs.put(&d_start, seg_start, (size_t)n * K1));
+    BILD_TRY(kc.bufs.put(&d_state, seg_state, (size_t)n * K1));
+    if (traj_id) BILD_TRY(kc.bufs.put(&d_tid, traj_id, (size_t)n));
     double *d_out[kKalOutputs] = {};
     for (int w = 0; w < kKalOutputs; ++w)
-        if (host_out[w]) SIM_TRY(kc.bufs.put(&d_out[w], nullptr, (size_t)(cand_max * row)));
+        if (host_out[w]) BILD_TRY(kc.bufs.put(&d_out[w], nullptr, (size_t)(cand_max * row)));
     for (size_t c = 0; c + 1 < cut.size(); ++c) {
         const int64_t c0 = cut[c], c1 = cut[c + 1];
-        SIM_TRY(kc.run(d_start, d_state, d_tid, traj_id, K1, c0, c1, d_out));
+        BILD_TRY(kc.run(d_start, d_state, d_tid, traj_id, K1, c0, c1, d_out));
         for (int w = 0; w < kKalOutputs; ++w)
             if (host_out[w])
                 HIP_TRY(hipMemcpyAsync(host_out[w] + c0 * row, d_out[w], (size_t)((c1 - c0) * row) * 8, hipMemcpyDeviceToHost, kc.bufs.stream));
@@ -274,7 +274,7 @@ extern "C" int bild_kalman_mixture(const bild_model *m, const bild_trajset *ts, 
     for (int64_t q = 0; q < nsel; ++q) gather(nref + q, order[q], traj_id ? traj_id[order[q]] : 0);
 
     KalCall kc(*m, *ts);
-    SIM_TRY(kc.init(Tout));
+    BILD_TRY(kc.init(Tout));
     // chunks: whole blocks (records, smoothed mean and variance, the block's partial sums), at least one block; the
     // reference tracks run in chunks of whole candidates under the same budget
     const int64_t budget = budget_bytes(scratch_bytes) / 8;
@@ -314,28 +314,28 @@ extern "C" int bild_kalman_mixture(const bild_model *m, const bild_trajset *ts, 
         }
         rcut.push_back(nref);
     }
-    SIM_TRY(kc.reserve(rec_max, cand_max));
+    BILD_TRY(kc.reserve(rec_max, cand_max));
     int32_t *d_start, *d_state, *d_tid, *d_ref_row, *d_blk_start, *d_blk_traj, *d_blk_T, *d_run_b0;
     double *d_ref, *d_w, *d_mean, *d_var, *d_part, *d_acc;
-    SIM_TRY(kc.bufs.put(&d_start, g_start.data(), g_start.size()));
-    SIM_TRY(kc.bufs.put(&d_state, g_state.data(), g_state.size()));
-    SIM_TRY(kc.bufs.put(&d_tid, g_tid.data(), g_tid.size()));
-    SIM_TRY(kc.bufs.put(&d_ref_row, ref_row.data(), ref_row.size()));
-    SIM_TRY(kc.bufs.put(&d_w, wts.data(), wts.size()));
-    SIM_TRY(kc.bufs.put(&d_blk_start, blk_start.data(), blk_start.size()));
-    SIM_TRY(kc.bufs.put(&d_blk_traj, blk_traj.data(), blk_traj.size()));
-    SIM_TRY(kc.bufs.put(&d_blk_T, blk_T.data(), blk_T.size()));
-    SIM_TRY(kc.bufs.put(&d_run_b0, nullptr, (size_t)blk_max + 1));
-    SIM_TRY(kc.bufs.put(&d_ref, nullptr, (size_t)(nref * row)));
-    SIM_TRY(kc.bufs.put(&d_mean, nullptr, (size_t)(cand_max * row)));
-    SIM_TRY(kc.bufs.put(&d_var, nullptr, (size_t)(cand_max * row)));
-    SIM_TRY(kc.bufs.put(&d_part, nullptr, (size_t)(blk_max * row * 3)));
-    SIM_TRY(kc.bufs.put(&d_acc, nullptr, (size_t)(nt * row * 3)));
+    BILD_TRY(kc.bufs.put(&d_start, g_start.data(), g_start.size()));
+    BILD_TRY(kc.bufs.put(&d_state, g_state.data(), g_state.size()));
+    BILD_TRY(kc.bufs.put(&d_tid, g_tid.data(), g_tid.size()));
+    BILD_TRY(kc.bufs.put(&d_ref_row, ref_row.data(), ref_row.size()));
+    BILD_TRY(kc.bufs.put(&d_w, wts.data(), wts.size()));
+    BILD_TRY(kc.bufs.put(&d_blk_start, blk_start.data(), blk_start.size()));
+    BILD_TRY(kc.bufs.put(&d_blk_traj, blk_traj.data(), blk_traj.size()));
+    BILD_TRY(kc.bufs.put(&d_blk_T, blk_T.data(), blk_T.size()));
+    BILD_TRY(kc.bufs.put(&d_run_b0, nullptr, (size_t)blk_max + 1));
+    BILD_TRY(kc.bufs.put(&d_ref, nullptr, (size_t)(nref * row)));
+    BILD_TRY(kc.bufs.put(&d_mean, nullptr, (size_t)(cand_max * row)));
+    BILD_TRY(kc.bufs.put(&d_var, nullptr, (size_t)(cand_max * row)));
+    BILD_TRY(kc.bufs.put(&d_part, nullptr, (size_t)(blk_max * row * 3)));
+    BILD_TRY(kc.bufs.put(&d_acc, nullptr, (size_t)(nt * row * 3)));
     HIP_TRY(hipMemsetAsync(d_acc, 0, (size_t)(nt * row * 3) * 8, kc.bufs.stream));
     for (size_t c = 0; c + 1 < rcut.size(); ++c) {
         double *o[kKalOutputs] = {};
         o[5] = d_ref + rcut[c] * row;
-        SIM_TRY(kc.run(d_start, d_state, d_tid, g_tid.data(), K1, rcut[c], rcut[c + 1], o));
+        BILD_TRY(kc.run(d_start, d_state, d_tid, g_tid.data(), K1, rcut[c], rcut[c + 1], o));
     }
     std::vector<int32_t> run_b0;
     for (size_t c = 0; c + 1 < bcut.size(); ++c) {
@@ -344,7 +344,7 @@ extern "C" int bild_kalman_mixture(const bild_model *m, const bild_trajset *ts, 
         double *o[kKalOutputs] = {};
         o[5] = d_mean;
         o[6] = d_var;
-        SIM_TRY(kc.run(d_start, d_state, d_tid, g_tid.data(), K1, c0, c1, o));
+        BILD_TRY(kc.run(d_start, d_state, d_tid, g_tid.data(), K1, c0, c1, o));
         run_b0.clear();
         for (int b = b0; b < b1; ++b)
             if (b == b0 || blk_traj[b] != blk_traj[b - 1]) run_b0.push_back(b - b0);
@@ -353,7 +353,7 @@ extern "C" int bild_kalman_mixture(const bild_model *m, const bild_trajset *ts, 
         std::vector<int32_t> lstart(blk_start.begin() + b0, blk_start.begin() + b1 + 1);
         for (int32_t &v : lstart) v -= blk_start[b0];
         int32_t *d_lstart;
-        SIM_TRY(kc.bufs.put(&d_lstart, lstart.data(), lstart.size()));
+        BILD_TRY(kc.bufs.put(&d_lstart, lstart.data(), lstart.size()));
         HIP_TRY(hipMemcpyAsync(d_run_b0, run_b0.data(), run_b0.size() * 4, hipMemcpyHostToDevice, kc.bufs.stream));
         MixParams mp{};
         mp.mean = d_mean;

@@ -36,6 +36,13 @@ int fail(int code, const char *fmt, ...);
                         "%s failed: %s", #call, hipGetErrorString(e_));                            \
     } while (0)
 
+// return on a code that is not BILD_OK
+#define BILD_TRY(x)                     \
+    do {                                \
+        int rc_ = (x);                  \
+        if (rc_ != BILD_OK) return rc_; \
+    } while (0)
+
 // A buffer that grows by a quarter beyond what is asked: device memory, or (Pinned) page-locked host staging -- copies to
 // and from that are true asynchronous DMA transfers
 template <bool Pinned> struct GrowBuf {

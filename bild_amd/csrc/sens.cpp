@@ -89,17 +89,17 @@ int project_all(const bild_model &m, int P, const bild_model_derivs *dm, int L, 
         auto at = [&](const double *a, size_t per) { return a ? a + (size_t)p * per : nullptr; };
         for (int s = 0; s < S; ++s) {
             const size_t o1 = ((size_t)p * S + s) * L;
-            SIM_TRY(project_matrix(m, at(dm->dB, nn), s, true, "dB", p, X));
+            BILD_TRY(project_matrix(m, at(dm->dB, nn), s, true, "dB", p, X));
             for (int i = 0; i < n; ++i) md.dlam[o1 + i] = X[(size_t)i * n + i];
-            SIM_TRY(project_matrix(m, at(dm->dSig, nn), s, true, "dSig", p, X));
+            BILD_TRY(project_matrix(m, at(dm->dSig, nn), s, true, "dSig", p, X));
             for (int i = 0; i < n; ++i) md.dsig[o1 + i] = X[(size_t)i * n + i];
-            SIM_TRY(project_matrix(m, at(dm->dC0, nn), s, false, "dC0", p, X));
+            BILD_TRY(project_matrix(m, at(dm->dC0, nn), s, false, "dC0", p, X));
             for (int i = 0; i < n; ++i)
                 for (int c = 0; c < n; ++c) md.dC0[(o1 + i) * L + c] = X[(size_t)i * n + c];
-            SIM_TRY(project_vectors(m, at(dm->dM0, nd), s, "dM0", p, X));
+            BILD_TRY(project_vectors(m, at(dm->dM0, nd), s, "dM0", p, X));
             for (int i = 0; i < n; ++i)
                 for (int k = 0; k < d; ++k) md.dM0[(o1 + i) * d + k] = X[(size_t)i * d + k];
-            SIM_TRY(project_vectors(m, at(dm->dG, nd), s, "dG", p, X));
+            BILD_TRY(project_vectors(m, at(dm->dG, nd), s, "dG", p, X));
             for (int i = 0; i < n; ++i)
                 for (int k = 0; k < d; ++k) {
                     md.dG[(o1 + i) * d + k] = X[(size_t)i * d + k];
@@ -171,19 +171,19 @@ extern "C" int bild_logl_sensitivities(const bild_model *m, const bild_trajset *
                     G[((size_t)s * L + i) * d + k] = m->Gq[((size_t)s * nm + i) * d + k];
                 }
             }
-        SIM_TRY(bufs.put(&sp.lam, lam.data(), lam.size()));
-        SIM_TRY(bufs.put(&sp.sig, sig.data(), sig.size()));
-        SIM_TRY(bufs.put(&sp.wq, wq.data(), wq.size()));
-        SIM_TRY(bufs.put(&sp.C0, C0.data(), C0.size()));
-        SIM_TRY(bufs.put(&sp.Q, Q.data(), Q.size()));
-        SIM_TRY(bufs.put(&sp.M0, M0.data(), M0.size()));
-        SIM_TRY(bufs.put(&sp.G, G.data(), G.size()));
-        SIM_TRY(bufs.put(&sp.dlam, md.dlam.data(), md.dlam.size()));
-        SIM_TRY(bufs.put(&sp.dsig, md.dsig.data(), md.dsig.size()));
-        SIM_TRY(bufs.put(&sp.dC0, md.dC0.data(), md.dC0.size()));
-        SIM_TRY(bufs.put(&sp.dM0, md.dM0.data(), md.dM0.size()));
-        SIM_TRY(bufs.put(&sp.dG, md.dG.data(), md.dG.size()));
-        SIM_TRY(bufs.put(&sp.ds2, ds2c.data(), ds2c.size()));
+        BILD_TRY(bufs.put(&sp.lam, lam.data(), lam.size()));
+        BILD_TRY(bufs.put(&sp.sig, sig.data(), sig.size()));
+        BILD_TRY(bufs.put(&sp.wq, wq.data(), wq.size()));
+        BILD_TRY(bufs.put(&sp.C0, C0.data(), C0.size()));
+        BILD_TRY(bufs.put(&sp.Q, Q.data(), Q.size()));
+        BILD_TRY(bufs.put(&sp.M0, M0.data(), M0.size()));
+        BILD_TRY(bufs.put(&sp.G, G.data(), G.size()));
+        BILD_TRY(bufs.put(&sp.dlam, md.dlam.data(), md.dlam.size()));
+        BILD_TRY(bufs.put(&sp.dsig, md.dsig.data(), md.dsig.size()));
+        BILD_TRY(bufs.put(&sp.dC0, md.dC0.data(), md.dC0.size()));
+        BILD_TRY(bufs.put(&sp.dM0, md.dM0.data(), md.dM0.size()));
+        BILD_TRY(bufs.put(&sp.dG, md.dG.data(), md.dG.size()));
+        BILD_TRY(bufs.put(&sp.ds2, ds2c.data(), ds2c.size()));
         // (the staging vectors go out of scope: the copies must have finished)
         HIP_TRY(hipStreamSynchronize(bufs.stream));
     }
@@ -199,10 +199,10 @@ extern "C" int bild_logl_sensitivities(const bild_model *m, const bild_trajset *
     const int64_t per = (int64_t)D * kSensStride + 2 * K1 + 1; // doubles (and int32 pairs, rounded up) per candidate
     const int64_t cmax = std::max<int64_t>(1, std::min<int64_t>(n, sim_scratch_bytes(scratch_bytes, free_b) / 8 / per));
     int32_t *d_start, *d_state, *d_tid = nullptr;
-    SIM_TRY(bufs.put(&d_start, nullptr, (size_t)(cmax * K1)));
-    SIM_TRY(bufs.put(&d_state, nullptr, (size_t)(cmax * K1)));
-    if (traj_id) SIM_TRY(bufs.put(&d_tid, nullptr, (size_t)cmax));
-    SIM_TRY(bufs.put(&sp.out, nullptr, (size_t)(cmax * D * kSensStride)));
+    BILD_TRY(bufs.put(&d_start, nullptr, (size_t)(cmax * K1)));
+    BILD_TRY(bufs.put(&d_state, nullptr, (size_t)(cmax * K1)));
+    if (traj_id) BILD_TRY(bufs.put(&d_tid, nullptr, (size_t)cmax));
+    BILD_TRY(bufs.put(&sp.out, nullptr, (size_t)(cmax * D * kSensStride)));
     std::vector<double> h_out((size_t)(cmax * D * kSensStride));
     for (int64_t c0 = 0; c0 < n; c0 += cmax) {
         const int64_t cn = std::min(cmax, n - c0);

@@ -87,24 +87,24 @@ extern "C" int bild_rouse_simulate(int S, int N, int d, const double *V, const d
     SimBufs bufs;
     HIP_TRY(hipStreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
     SimParams p{};
-    SIM_TRY(bufs.put(&p.V, V, SNN));
-    SIM_TRY(bufs.put(&p.Vt, Vt.data(), SNN));
-    SIM_TRY(bufs.put(&p.b, b, SN));
-    SIM_TRY(bufs.put(&p.ssig, sqrt_sig, SN));
-    SIM_TRY(bufs.put(&p.scinf, sqrt_cinf, SN));
-    SIM_TRY(bufs.put(&p.g, VtG, SND));
-    SIM_TRY(bufs.put(&p.m0, VtM0, SND));
-    SIM_TRY(bufs.put(&p.u, u.data(), SN));
-    SIM_TRY(bufs.put(&p.T, T, n));
-    SIM_TRY(bufs.put(&p.frame_off, frame_off.data(), n));
-    SIM_TRY(bufs.put(&p.seg_start, seg_start, (size_t)n * K1));
-    SIM_TRY(bufs.put(&p.seg_state, seg_state, (size_t)n * K1));
+    BILD_TRY(bufs.put(&p.V, V, SNN));
+    BILD_TRY(bufs.put(&p.Vt, Vt.data(), SNN));
+    BILD_TRY(bufs.put(&p.b, b, SN));
+    BILD_TRY(bufs.put(&p.ssig, sqrt_sig, SN));
+    BILD_TRY(bufs.put(&p.scinf, sqrt_cinf, SN));
+    BILD_TRY(bufs.put(&p.g, VtG, SND));
+    BILD_TRY(bufs.put(&p.m0, VtM0, SND));
+    BILD_TRY(bufs.put(&p.u, u.data(), SN));
+    BILD_TRY(bufs.put(&p.T, T, n));
+    BILD_TRY(bufs.put(&p.frame_off, frame_off.data(), n));
+    BILD_TRY(bufs.put(&p.seg_start, seg_start, (size_t)n * K1));
+    BILD_TRY(bufs.put(&p.seg_state, seg_state, (size_t)n * K1));
     uint8_t *d_missing;
-    SIM_TRY(bufs.put(&d_missing, missing, rows));
+    BILD_TRY(bufs.put(&d_missing, missing, rows));
     if (!missing) HIP_TRY(hipMemsetAsync(d_missing, 0, rows, bufs.stream));
     p.missing = d_missing;
-    SIM_TRY(bufs.put(&p.err, loc_err, (size_t)n * d));
-    SIM_TRY(bufs.put(&p.out, nullptr, rows * d));
+    BILD_TRY(bufs.put(&p.err, loc_err, (size_t)n * d));
+    BILD_TRY(bufs.put(&p.out, nullptr, rows * d));
     p.K1 = K1;
     p.S = S;
     p.N = N;
@@ -127,11 +127,11 @@ extern "C" int bild_rouse_simulate(int S, int N, int d, const double *V, const d
         return (int)BILD_OK;
     };
     if (!normals) {
-        SIM_TRY(launch(p, 0, n));
+        BILD_TRY(launch(p, 0, n));
     } else {
         double *d_z;
-        SIM_TRY(bufs.put(&d_z, nullptr, (size_t)scratch_doubles));
-        SIM_TRY(bufs.put(&p.z_off, z_off.data(), n));
+        BILD_TRY(bufs.put(&d_z, nullptr, (size_t)scratch_doubles));
+        BILD_TRY(bufs.put(&p.z_off, z_off.data(), n));
         p.z = d_z;
         for (int first = 0; first < n;) {
             const int last = sim_chunk_end(z_off, first, n, scratch_doubles);
@@ -139,7 +139,7 @@ extern "C" int bild_rouse_simulate(int S, int N, int d, const double *V, const d
             HIP_TRY(hipMemcpyAsync(d_z, normals + z_off[first], (size_t)(z_off[last] - z_off[first]) * 8, hipMemcpyHostToDevice,
                                    bufs.stream));
             p.z_first = z_off[first];
-            SIM_TRY(launch(p, first, last - first));
+            BILD_TRY(launch(p, first, last - first));
             first = last;
         }
     }

@@ -27,12 +27,6 @@ struct SimBufs {
     }
 };
 
-#define SIM_TRY(x)                      \
-    do {                                \
-        int rc_ = (x);                  \
-        if (rc_ != BILD_OK) return rc_; \
-    } while (0)
-
 // the upload budget of the normals: the caller's scratch_bytes, or at most 1 GiB and a third of the free memory
 inline int64_t sim_scratch_bytes(int64_t scratch_bytes, size_t free_bytes)
 {
