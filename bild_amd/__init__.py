@@ -18,6 +18,7 @@ from .exact import exact_evidence, ExactResult, exact_sample, ExactSamplingResul
 from .exact import exact_sensitivities, EvidenceSensitivities  # noqa: F401
 from .exact import DwellPrior, exact_dwell, ExactDwellResults, fit_markov_prior, MarkovPriorFit  # noqa: F401
 from .exact import exact_dwell_draw, ExactDwellDraws  # noqa: F401
+from .exact import exact_dwell_sensitivities, DwellSensitivities  # noqa: F401
 from .amis import FixedkSampler, Dirichlet, CFC  # noqa: F401
 from .profiles import Loopingprofile  # noqa: F401
 from .trajectory import Trajectory  # noqa: F401

@@ -176,6 +176,9 @@ _SIGNATURES = {
     # exact posterior draws under a dwell-time prior (gauss_dwelldraw.cpp)
     'bild_gauss_dwell_draw': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _ip,
                                              _vp, ctypes.c_int, _dp, ctypes.c_uint64, _vp]),
+    # gradient of the exact evidence under a dwell-time prior (gauss_dwellsens.cpp)
+    'bild_gauss_dwell_sensitivities': (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_uint, ctypes.c_int, _vp,
+                                                      ctypes.c_int64, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1383,6 +1386,42 @@ def gauss_dwell_evidence(model, ts, log_init, log_jump, log_dwell, log_surv, mar
     spec = DwellOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
     check(lib().bild_gauss_dwell_evidence(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
                                           DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
+    return res
+
+
+class DwellsensOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'n_nan_windows', 'grad', 'exp_logl', 'fisher')]
+
+
+def gauss_dwell_sensitivities(model, ts, trajs, log_init, log_jump, log_dwell, log_surv, dmsd=None, dmsd_inf=None, dmean=None, P=0,
+                              omit=False, fisher=True, scratch_bytes=0):
+    """
+    gradient of the exact evidence under a dwell-time prior of every trajectory of the set (bild_gauss_dwell_sensitivities):
+    trajs the (T, d) arrays the set was built from, the prior's tables as for `gauss_dwell_evidence`, derivatives as for
+    `gauss_logl_sensitivities`.  A dict of logev, exp_logl (n_traj,), n_nan_windows (n_traj,) int64, grad (n_traj, P) and
+    fisher (n_traj, P, P) or None
+    """
+    S, d, L1 = model.S, model.d, model.Tmax + 1
+    log_init, log_jump, log_dwell, log_surv = f64(log_init), f64(log_jump), f64(log_dwell), f64(log_surv)
+    L = log_dwell.shape[1]
+    assert log_init.shape == (S,) and log_jump.shape == (S, S) and log_dwell.shape == (S, L) and log_surv.shape == (S, L)
+    n = ts.n_traj
+    arrs = [f64(t) for t in trajs]
+    assert len(arrs) == n and all(len(a) == T for a, T in zip(arrs, ts.T))
+    x = f64(np.concatenate(arrs, axis=0))
+    keep = {}
+    for name, a, shape in (('dmsd', dmsd, (P, S, d, L1)), ('dmsd_inf', dmsd_inf, (P, S, d)), ('dmean', dmean, (P, S, d))):
+        if a is not None:
+            a = f64(a)
+            assert a.shape == shape, f"{name} has shape {a.shape}, expected {shape}"
+            keep[name] = a
+    derivs = GaussDerivs(**{k: aptr(a) if a.size else None for k, a in keep.items()})
+    res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'grad': np.empty((n, P)), 'exp_logl': np.empty(n),
+           'fisher': np.empty((n, P, P)) if fisher else None}
+    spec = DwellsensOut(**{name: (aptr(a) if a is not None and a.size else None) for name, a in res.items()})
+    check(lib().bild_gauss_dwell_sensitivities(model._h, ts._h, dptr(x), L, dptr(log_init), dptr(log_jump), dptr(log_dwell),
+                                               dptr(log_surv), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(P),
+                                               ctypes.byref(derivs), int(scratch_bytes), ctypes.byref(spec)))
     return res
 
 

@@ -111,6 +111,10 @@ int launch_dwell_cover(const DwellParams &, void *) { return 1; }
 int launch_dwell_carry(const DwellParams &, void *) { return 1; }
 int launch_dwell_counts(const DwellParams &, void *) { return 1; }
 } // namespace bild
+#include "gauss_dwellsens.h"
+namespace bild {
+int launch_dwellsens_weight(const DwellParams &, const DwellsensWeights &, void *) { return 1; }
+}
 #include "gauss_dwelldraw.h"
 namespace bild {
 int launch_dwelldraw_head(const DwelldrawParams &, void *) { return 1; }

@@ -1,6 +1,7 @@
 // The frame of one exact-inference call (exact.cpp, gauss_segdp.cpp, gauss_segdraw.cpp, gauss_segsens.cpp, gauss_dwell.cpp,
-// gauss_dwelldraw.cpp): the lock that serialises the calls on a stream, the stream, the device memory of the call and the
-// rule that cuts the call into chunks.  Host only; private to the library.
+// gauss_dwelldraw.cpp, gauss_dwellsens.cpp; gauss_segtangent.cpp allocates through it): the lock that serialises the calls on
+// a stream, the stream, the device memory of the call and the rule that cuts the call into chunks.  Host only; private to the
+// library.
 #pragma once
 #include "internal.h"
 #include "likelihood.h"

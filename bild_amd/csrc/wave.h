@@ -1,5 +1,5 @@
 // What the kernels of the exact-inference calls share (gauss_segdp.hip, gauss_segdraw.hip, gauss_segsens.hip, gauss_dwell.hip,
-// gauss_dwelldraw.hip): the two constants, the reductions and scans across the 64 lanes of a wavefront, the step of an
+// gauss_dwelldraw.hip, gauss_dwellsens.hip): the two constants, the reductions and scans across the 64 lanes of a wavefront, the step of an
 // inverse-CDF pick, the carry of the marginals and the uniforms of a draw.  Every function does its operations in one fixed
 // order, so a kernel that calls it sums as the others do.  Device code only.
 #pragma once

@@ -21,6 +21,9 @@ counts; `fit_markov_prior` fits a Markov prior's switching rates to a data set b
 
 `exact_dwell_draw` (bild_gauss_dwell_draw) draws profiles from the exact posterior under that prior,
 segment by segment against the backward tables of the dwell-time recursion.
+
+`exact_dwell_sensitivities` (bild_gauss_dwell_sensitivities) is the gradient of `exact_dwell`'s evidence
+with respect to model parameters; `GenericGaussianModel.fit_dwell` fits a model, and a Markov prior with it, on that gradient.
 """
 import math
 import warnings
@@ -916,6 +919,39 @@ class MarkovPriorFit:
         return DwellPrior.markov(self.P, self.init, n=n)
 
 
+class EvidenceNotFinite(ValueError):
+    """ `fit_markov_prior`: the total log evidence of the data set is NaN or -inf; ``total`` holds it """
+
+    def __init__(self, total):
+        self.total = float(total)
+        super().__init__(f"the total log evidence is {total}: " + ("a trajectory has NaN windows, use nan='omit'"
+                                                                   if np.isnan(total) else "a trajectory has no profile of positive weight"))
+
+
+def _markov_start(model, start):
+    """ `fit_markov_prior`'s start -> (allowed (S, S) off-diagonal transitions, P (S, S), init (S,)), checked """
+    S = model.msd.shape[0]
+    allowed = np.asarray(model.transitions, dtype=bool).copy()
+    if allowed.shape != (S, S):
+        raise ValueError(f"model.transitions has shape {allowed.shape}; ({S}, {S}) expected")
+    np.fill_diagonal(allowed, False)
+    init = None
+    if start is None:
+        n_out = allowed.sum(axis=1)
+        P = np.where(allowed, 0.1 / np.maximum(n_out, 1)[:, None], 0.0)
+        P[np.arange(S), np.arange(S)] = 1.0 - P.sum(axis=1)
+    else:
+        if isinstance(start, tuple):
+            start, init = start
+        P = np.array(start, dtype=np.float64)
+        if P.shape != (S, S):
+            raise ValueError(f"start has shape {P.shape}; ({S}, {S}) expected")
+        if np.any((P > 0) & ~allowed & ~np.eye(S, dtype=bool)):
+            raise ValueError("start has a positive entry that model.transitions forbids")
+    init = np.full(S, 1.0 / S) if init is None else np.array(init, dtype=np.float64)
+    return allowed, P, init
+
+
 def fit_markov_prior(trajs, model, start=None, tol=1e-8, max_iter=200, nan='propagate'):
     """
     Maximum-likelihood switching rates of a data set: EM over the transition matrix P and the initial distribution of a Markov
@@ -938,24 +974,7 @@ def fit_markov_prior(trajs, model, start=None, tol=1e-8, max_iter=200, nan='prop
         raise TypeError(f"fit_markov_prior needs a GenericGaussianModel, whose log-likelihood is a sum of segment terms, not "
                         f"{type(model).__name__}")
     S = model.msd.shape[0]
-    allowed = np.asarray(model.transitions, dtype=bool).copy()
-    if allowed.shape != (S, S):
-        raise ValueError(f"model.transitions has shape {allowed.shape}; ({S}, {S}) expected")
-    np.fill_diagonal(allowed, False)
-    init = None
-    if start is None:
-        n_out = allowed.sum(axis=1)
-        P = np.where(allowed, 0.1 / np.maximum(n_out, 1)[:, None], 0.0)
-        P[np.arange(S), np.arange(S)] = 1.0 - P.sum(axis=1)
-    else:
-        if isinstance(start, tuple):
-            start, init = start
-        P = np.array(start, dtype=np.float64)
-        if P.shape != (S, S):
-            raise ValueError(f"start has shape {P.shape}; ({S}, {S}) expected")
-        if np.any((P > 0) & ~allowed & ~np.eye(S, dtype=bool)):
-            raise ValueError("start has a positive entry that model.transitions forbids")
-    init = np.full(S, 1.0 / S) if init is None else np.array(init, dtype=np.float64)
+    allowed, P, init = _markov_start(model, start)
     if not (tol > 0) or isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
         raise ValueError(f"tol = {tol!r} must be positive and max_iter = {max_iter!r} a positive integer")
     single = not isinstance(trajs, (list, tuple))
@@ -973,8 +992,7 @@ def fit_markov_prior(trajs, model, start=None, tol=1e-8, max_iter=200, nan='prop
                                         marginals=True, omit=nan == 'omit')
         total = float(np.sum(res['logev']))
         if not np.isfinite(total):
-            raise ValueError(f"the total log evidence is {total}: " + ("a trajectory has NaN windows, use nan='omit'"
-                                                                       if np.isnan(total) else "a trajectory has no profile of positive weight"))
+            raise EvidenceNotFinite(total)
         history.append(total)
         jumps, stay = res['exp_jumps'].sum(axis=0), res['exp_stay'].sum(axis=0)
         jumps = np.where(allowed, jumps, 0.0)
@@ -991,3 +1009,63 @@ def fit_markov_prior(trajs, model, start=None, tol=1e-8, max_iter=200, nan='prop
             converged = True
             break
     return MarkovPriorFit(P=P, init=init, log_evidence=np.array(history), n_iter=len(history), converged=converged)
+
+
+# ---------------------------------------------------------------- gradient of the evidence under the dwell-time prior (section 23)
+
+class DwellSensitivities:
+    """
+    `exact_dwell_sensitivities` of n trajectories and P parameters:
+
+    log_evidence : (n,) the log evidence under the prior, the numbers `exact_dwell` gives
+    n_nan_windows : (n,) int64, as `exact_dwell` counts them
+    grad : (n, P) the gradient of ``log_evidence`` with respect to the parameters
+    expected_logL : (n,) the posterior mean of the log-likelihood
+    fisher : (n, P, P) or None; the posterior mean of the complete-data information (innovations form).  A scoring matrix:
+        the information of the marginal likelihood is smaller, so it does not give standard errors.
+
+    A trajectory with NaN windows under ``nan='propagate'`` is NaN in all but ``n_nan_windows``; a trajectory without a profile
+    of positive weight has ``log_evidence`` -inf and NaN in ``grad``, ``expected_logL`` and ``fisher``.
+    """
+
+    __slots__ = ('log_evidence', 'n_nan_windows', 'grad', 'expected_logL', 'fisher')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return f"DwellSensitivities(n={len(self.log_evidence)}, P={self.grad.shape[1]})"
+
+
+def exact_dwell_sensitivities(trajs, model, prior, dmsd=None, dmsd_inf=None, dmean=None, nan='propagate', fisher=True, scratch_bytes=0):
+    """
+    The gradient of the exact evidence of `exact_dwell` with respect to P <= 4 model parameters, for trajectories whose looping
+    profile is not known (bild_gauss_dwell_sensitivities).  The prior does not depend on the model's
+    parameters, so by Fisher's identity the gradient is the posterior mean over all profiles of the gradient of the
+    log-likelihood; the posterior weights of the segments come from the forward and backward tables of the dwell-time
+    recursion, the gradients from forward tangents of every window's Cholesky factor.  No sampler, no noise, no k_max.
+
+    trajs : a trajectory or a list of them (one device call)
+    model : a `GenericGaussianModel` with at most 4 states (anything else: TypeError)
+    prior : a `DwellPrior` over the model's states whose tables cover the longest trajectory
+    dmsd, dmsd_inf, dmean : the derivatives of the model's tables, as `GenericGaussianModel.logL_sensitivities` takes them
+    nan : as for `exact_dwell`.  Under 'propagate' a trajectory with NaN windows is NaN; under 'omit' those windows weigh 0.
+    fisher : return the posterior-weighted Fisher matrix.  It is the posterior mean of the complete-data information, a
+        scoring matrix for a fit; it is NOT the information of the marginal likelihood, which is smaller by the posterior
+        covariance of the score, so it does not give standard errors.
+    scratch_bytes : device workspace of one chunk (0: the library's rule)
+
+    Every refusal is raised before the trajectories are uploaded.  Returns `DwellSensitivities`.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    P, given = model._derivative_arrays(dmsd, dmsd_inf, dmean)
+    if not items:
+        return DwellSensitivities(log_evidence=np.zeros(0), n_nan_windows=np.zeros(0, dtype=np.int64), grad=np.zeros((0, P)),
+                                  expected_logL=np.zeros(0), fisher=np.zeros((0, P, P)) if fisher else None)
+    arrs = model._direct_arrays(items)
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_dwell_sensitivities(model.handle(), ts, arrs, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
+                                         P=P, omit=nan == 'omit', fisher=fisher, scratch_bytes=scratch_bytes, **given)
+    return DwellSensitivities(log_evidence=res['logev'], n_nan_windows=res['n_nan_windows'], grad=res['grad'],
+                              expected_logL=res['exp_logl'], fisher=res['fisher'])

@@ -455,6 +455,129 @@ class GenericGaussianModel(MultiStateModel):
         res.n_iter += 2 * P
         return res
 
+    @classmethod
+    def fit_dwell(cls, trajs, family, start, prior=None, markov_start=None, derivatives=None, nan='propagate', tol=1e-8, max_iter=50,
+                  prior_tol=1e-10, prior_max_iter=200):
+        """
+        Maximum-likelihood fit of positive parameters theta on trajectories whose looping profiles are NOT known, under a
+        dwell-time prior on the profiles: `fit_marginal`'s contract with `bild_amd.exact_dwell`'s evidence (one per
+        trajectory, no k and no k_max) in place of the k-uniform marginal.  The gradient is exact
+        (`bild_amd.exact_dwell_sensitivities`).
+
+        trajs, family, start, derivatives, tol, max_iter : as for `fit`
+        prior : a `DwellPrior` -- held fixed: an evaluation is the model of the trial theta, its trajectory set and one
+            `exact_dwell_sensitivities` call.  None -- a Markov prior is fitted along with the model by the profile
+            likelihood: an evaluation builds the model and its trajectory set, runs `bild_amd.fit_markov_prior` on that set
+            (one build per evaluation: the inner EM and the gradient call share the cached set), warm-started from the
+            (P, init) of the last accepted evaluation, and makes one `exact_dwell_sensitivities` call at the fitted prior.
+            The objective is the total log evidence at (theta, P^(theta)), the full maximum-likelihood fit of the hidden
+            semi-Markov model on exact evidence.
+        markov_start : ``prior=None`` only: the start of the first inner fit, as `fit_markov_prior` takes it (None, P or
+            (P, init))
+        nan : as for `exact_dwell`
+        prior_tol, prior_max_iter : ``tol`` and ``max_iter`` of the inner `fit_markov_prior`
+
+        With ``prior=None`` the theta-gradient of the profile likelihood is taken as the partial gradient at P^(theta), by the
+        envelope theorem.  That rests on the inner EM having converged: at an EM fixed point the derivative of the evidence
+        with respect to P vanishes, short of it a term of the size of the last EM step times dP^/dtheta is left out.  This is
+        why ``prior_tol`` is deliberately tighter than ``tol``.
+
+        The steps are Fisher scoring in log theta with the posterior mean of the complete-data information as the matrix;
+        the standard errors come, as in `fit_marginal`, from the observed information: central differences in log theta
+        (step 1e-4) of the exact gradient at the optimum, symmetrised -- 2 P further evaluations, each of which re-profiles P,
+        counted in ``n_iter``.  With ``prior=None`` they are therefore those of the profile likelihood.  No standard errors are
+        given for P.  ``logL`` holds the total log evidence; ``prior_fit`` the `MarkovPriorFit` of the accepted evaluation
+        (None under a fixed prior).  A NaN or -inf objective at the start raises ValueError; at a trial theta it rejects the step,
+        with either kind of prior (the inner fit's `EvidenceNotFinite` is taken as that objective).
+        """
+        from .exact import DwellPrior, EvidenceNotFinite, exact_dwell_sensitivities, fit_markov_prior, _check_exact_dwell, _markov_start
+        start = dict(start)
+        params = tuple(start)
+        if not params:
+            raise ValueError("nothing to fit: start is empty")
+        if len(params) > 4:
+            raise ValueError("at most 4 parameters")
+        theta = np.array([float(start[p]) for p in params])
+        if np.any(~np.isfinite(theta)) or np.any(theta <= 0):
+            raise ValueError(f"parameters must be positive and finite: {start}")
+        if tol <= 0 or max_iter < 1:
+            raise ValueError("need tol > 0 and max_iter >= 1")
+        if not (prior_tol > 0) or isinstance(prior_max_iter, bool) or not isinstance(prior_max_iter, (int, np.integer)) or prior_max_iter < 1:
+            raise ValueError(f"prior_tol = {prior_tol!r} must be positive and prior_max_iter = {prior_max_iter!r} a positive integer")
+        items = list(trajs) if isinstance(trajs, (list, tuple)) else [trajs]
+        if not items:
+            raise ValueError("need at least one trajectory")
+        if prior is not None and not isinstance(prior, DwellPrior):
+            raise TypeError(f"prior must be a DwellPrior or None, not {type(prior).__name__}")
+        if prior is not None and markov_start is not None:
+            raise ValueError("markov_start starts the fit of a Markov prior: it needs prior=None")
+        probe = cls(family(**dict(zip(params, theta))))
+        n_frames = max(len(t) for t in items)
+        if prior is None:
+            _, P0, init0 = _markov_start(probe, markov_start)
+            _check_exact_dwell(items, probe, DwellPrior.markov(P0, init0, n=n_frames), nan)
+        else:
+            _check_exact_dwell(items, probe, prior, nan)
+        state = {'warm': markov_start, 'best': -np.inf, 'fit': None, 'frozen': False}
+
+        def evaluate(th):
+            kw = dict(zip(params, th))
+            model = cls(family(**kw))
+            if derivatives is not None:
+                dmsd, dmsd_inf, dmean = derivatives(**kw)
+            else:
+                dmsd, dmsd_inf, dmean = _log_differences(cls, family, params, th)
+            model._derivative_arrays(dmsd, dmsd_inf, dmean)     # (refused before the set is built)
+            pf, pr = None, prior
+            if prior is None:
+                try:
+                    pf = fit_markov_prior(items, model, start=state['warm'], tol=prior_tol, max_iter=int(prior_max_iter), nan=nan)
+                except EvidenceNotFinite as e:
+                    # the objective is e.total here: NaN at the start raises below; a trial theta is rejected as a step and damped,
+                    # as under a fixed prior
+                    P = len(th)
+                    return model, e.total, np.zeros(P), np.zeros((P, P))
+                pr = pf.prior(n_frames)
+            r = exact_dwell_sensitivities(items, model, pr, dmsd=dmsd, dmsd_inf=dmsd_inf, dmean=dmean, nan=nan)
+            g, F = _log_chain_rule(r.grad, r.fisher, np.broadcast_to(th, r.grad.shape))
+            total = float(r.log_evidence.sum())
+            # `_fisher_scoring`'s acceptance rule (noted there as well): the start, then every evaluation whose objective is
+            # finite and strictly larger than every one before
+            if not state['frozen'] and np.isfinite(total) and total > state['best']:
+                state['best'], state['fit'] = total, pf
+                if pf is not None:
+                    state['warm'] = (pf.P, pf.init)
+            return model, total, g.sum(axis=0), F.sum(axis=0)
+
+        first = evaluate(theta)
+        if np.isnan(first[1]):
+            hint = " (a trajectory has NaN windows: a later ss_order-0 segment without a valid frame; try nan='omit')" \
+                if nan == 'propagate' else ""
+            raise ValueError(f"the log evidence is NaN at the start{hint}")
+        if first[1] == -np.inf:
+            raise ValueError("the log evidence is -inf at the start: a trajectory has no profile of positive weight")
+        calls = [first]
+
+        def cached(th):     # the start is evaluated once
+            return calls.pop() if calls else evaluate(th)
+
+        res = _fisher_scoring(cached, theta, params, tol, max_iter)
+        state['frozen'] = True
+        res.prior_fit = state['fit']
+        th = np.array([res.params[p] for p in params])
+        P, h = len(params), _MARGINAL_INFO_STEP
+        H = np.zeros((P, P))
+        for p in range(P):
+            e = np.zeros(P)
+            e[p] = h
+            H[:, p] = -(evaluate(th * np.exp(e))[2] - evaluate(th * np.exp(-e))[2]) / (2 * h)
+        H = 0.5 * (H + H.T)
+        cov = np.linalg.pinv(H) * np.outer(th, th)
+        res.cov = cov
+        res.se = dict(zip(params, np.sqrt(np.maximum(np.diag(cov), 0.))))
+        res.n_iter += 2 * P
+        return res
+
     # ------------------------------------------------------------------ generative model
     def trajectory_from_loopingprofile(self, profile, missing_frames=None, rng=None):
         """

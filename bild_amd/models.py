@@ -716,12 +716,14 @@ class FitResult:
     """
     `MultiStateRouse.fit`, `GenericGaussianModel.fit`: ``model`` (at the fitted parameters), ``params`` and ``se`` (dicts by name), ``cov`` (P x P, in
     the order of ``names``), ``logL`` (total at the optimum), ``n_iter`` (device calls), ``converged``, ``history``
-    (accepted (params, logL) in order, the start first)
+    (accepted (params, logL) in order, the start first); ``prior_fit``: the `MarkovPriorFit` of the accepted evaluation where
+    `GenericGaussianModel.fit_dwell` fitted a Markov prior along with the model, None for every other fit
     """
 
-    def __init__(self, model, params, se, cov, logL, n_iter, converged, history, names):
+    def __init__(self, model, params, se, cov, logL, n_iter, converged, history, names, prior_fit=None):
         self.model, self.params, self.se, self.cov, self.logL = model, params, se, cov, logL
         self.n_iter, self.converged, self.history, self.names = n_iter, converged, history, tuple(names)
+        self.prior_fit = prior_fit
 
     def __repr__(self):
         ps = ', '.join(f"{k}={v:.6g}+-{self.se[k]:.2g}" for k, v in self.params.items())
@@ -753,6 +755,10 @@ def _fisher_scoring(evaluate, theta, params, tol, max_iter):
     gradient and Fisher information with respect to log theta).  Stops when the Newton decrement falls below ``tol``, after
     ``max_iter`` evaluations, or when the damping exceeds 1e12; a step is accepted only if the logL rises.  -> `FitResult`
     with standard errors from the inverse Fisher information by the delta method.
+
+    The acceptance rule -- the start, then a trial whose logL is finite and strictly larger than the current one -- is mirrored
+    by `GenericGaussianModel.fit_dwell`'s ``evaluate``, which has to know which evaluation was accepted (its warm start and
+    `FitResult.prior_fit`): change the two together.
     """
     model, L, g, F = evaluate(theta)
     history = [(dict(zip(params, theta)), L)]

@@ -1059,6 +1059,46 @@ int bild_gauss_dwell_draw(const bild_gauss_model *m, const bild_gauss_trajset *t
                           int64_t n_draws, const int32_t *draw_traj, const int64_t *draw_stream, int U, const double *uniforms,
                           uint64_t seed, bild_dwelldraw_out *out);
 
+/* ---------------------------------------------------------------- evidence sensitivities under a dwell-time prior ----
+ * GenericGaussianModel only, at most 4 states.  The gradient of logev of bild_gauss_dwell_evidence (same
+ * tables, same NaN flag; the same number, bit for bit: the same forward kernel) with respect to P <= 4 model parameters, for
+ * trajectories whose profile is not known.  The prior does not depend on the parameters, so by Fisher's identity the
+ * gradient is the posterior mean of the gradient of the log-likelihood.  With the tables of the block before the last,
+ *   Q(a, b, s) = exp(alpha(a, s) + omega_s(a, b) + W[s][a - 1][b] + gamma(b, s) - logev)      (a = 0: log_init[s] and F)
+ * the posterior probability of the segment [a, b) in state s, alpha(a, s) = log sum_s' exp(A(a, s') + log_jump[s'][s]), and
+ *   Omega(s, a, t) = sum_{b > t} Q(a, b, s)
+ * the posterior probability that a segment in state s starts at a and has not ended by frame t.  Per trajectory:
+ *   logev          as bild_gauss_dwell_evidence gives it
+ *   n_nan_windows  as bild_gauss_dwell_evidence gives it
+ *   grad           P values: d logev / d theta_p = - sum Omega(s, a, t_j) dtau_p over the entries j of the window that starts
+ *                  at a - 1 (the first window for a = 0), tau and dtau those of bild_gauss_logl_sensitivities
+ *   exp_logl       - sum Omega tau: the posterior mean of the log-likelihood
+ *   fisher         P x P: sum Omega (2 a_p a_q + g_p g_q), the innovations form of bild_gauss_logl_sensitivities,
+ *                  posterior-weighted.  This is the posterior mean of the complete-data information: a scoring matrix for a
+ *                  fit.  It is NOT the information of the marginal likelihood, which is smaller by the posterior covariance
+ *                  of the score; standard errors need the latter.
+ * x and the derivatives as for bild_gauss_segment_sensitivities.  flags = 0 (BILD_DWELL_NAN_PROPAGATE): a trajectory with
+ * n_nan_windows > 0 has NaN in logev, grad, exp_logl and fisher; the other trajectories are untouched.
+ * BILD_DWELL_NAN_OMIT: the skipped windows weigh 0.  A trajectory without a profile of positive weight has logev -inf and
+ * NaN in grad, exp_logl and fisher.  NULL outputs are not written.  No atomics, fixed summation orders that depend on the
+ * trajectory alone: results are bit-identical across calls, the order of the set, a trajectory alone or in a batch, and
+ * scratch_bytes (chunks of whole trajectories, and of factorisations of windows with a missing frame; 0: at most 1 GiB
+ * and a third of the free device memory).  tau sums do not depend on P.  Refused before any device work: what
+ * bild_gauss_dwell_evidence refuses (there is no T_max here) and what bild_gauss_logl_sensitivities refuses.  Plain
+ * launches on the set's stream.  Synchronous. */
+typedef struct bild_dwellsens_out {
+    double *logev;                          /* n_traj */
+    int64_t *n_nan_windows;                 /* n_traj */
+    double *grad;                           /* n_traj x P */
+    double *exp_logl;                       /* n_traj */
+    double *fisher;                         /* n_traj x P x P */
+} bild_dwellsens_out;                       /* every pointer may be NULL: not written */
+
+int bild_gauss_dwell_sensitivities(const bild_gauss_model *m, const bild_gauss_trajset *ts, const double *x, int L,
+                                   const double *log_init, const double *log_jump, const double *log_dwell,
+                                   const double *log_surv, unsigned flags, int P, const bild_gauss_derivs *dm,
+                                   int64_t scratch_bytes, bild_dwellsens_out *out);
+
 #ifdef __cplusplus
 }
 #endif
