@@ -179,6 +179,9 @@ _SIGNATURES = {
     # gradient of the exact evidence under a dwell-time prior (gauss_dwellsens.cpp)
     'bild_gauss_dwell_sensitivities': (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_uint, ctypes.c_int, _vp,
                                                       ctypes.c_int64, _vp]),
+    # expected segment-length counts under a dwell-time prior (gauss_dwelllen.cpp)
+    'bild_gauss_dwell_lengths': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_uint, ctypes.c_int64,
+                                                _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1422,6 +1425,30 @@ def gauss_dwell_sensitivities(model, ts, trajs, log_init, log_jump, log_dwell, l
     check(lib().bild_gauss_dwell_sensitivities(model._h, ts._h, dptr(x), L, dptr(log_init), dptr(log_jump), dptr(log_dwell),
                                                dptr(log_surv), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(P),
                                                ctypes.byref(derivs), int(scratch_bytes), ctypes.byref(spec)))
+    return res
+
+
+class DwellLengthsOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'n_nan_windows', 'exp_jumps', 'exp_init', 'exp_dwell', 'exp_cens')]
+
+
+def gauss_dwell_lengths(model, ts, log_init, log_jump, log_dwell, log_surv, omit=False, scratch_bytes=0):
+    """
+    expected segment-length counts under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_lengths): a dict
+    of logev (n_traj,), n_nan_windows (n_traj,) int64, exp_jumps (n_traj, S, S), exp_init (n_traj, S), exp_dwell and exp_cens
+    (n_traj, S, T_max), length l at column l - 1, 0 behind a trajectory's T; T_max the set's longest trajectory
+    """
+    S = model.S
+    log_init, log_jump, log_dwell, log_surv = f64(log_init), f64(log_jump), f64(log_dwell), f64(log_surv)
+    L = log_dwell.shape[1]
+    assert log_init.shape == (S,) and log_jump.shape == (S, S) and log_dwell.shape == (S, L) and log_surv.shape == (S, L)
+    n = ts.n_traj
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'exp_jumps': np.empty((n, S, S)),
+           'exp_init': np.empty((n, S)), 'exp_dwell': np.empty((n, S, T_max)), 'exp_cens': np.empty((n, S, T_max))}
+    spec = DwellLengthsOut(**{name: aptr(a) for name, a in res.items()})
+    check(lib().bild_gauss_dwell_lengths(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
+                                         DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
     return res
 
 

@@ -115,6 +115,10 @@ int launch_dwell_counts(const DwellParams &, void *) { return 1; }
 namespace bild {
 int launch_dwellsens_weight(const DwellParams &, const DwellsensWeights &, void *) { return 1; }
 }
+#include "gauss_dwelllen.h"
+namespace bild {
+int launch_dwell_lengths(const DwellParams &, const DwellLengths &, void *) { return 1; }
+}
 #include "gauss_dwelldraw.h"
 namespace bild {
 int launch_dwelldraw_head(const DwelldrawParams &, void *) { return 1; }

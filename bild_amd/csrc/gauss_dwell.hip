@@ -400,7 +400,7 @@ __global__ void __launch_bounds__(64) dwell_counts_kernel(DwellParams p)
             acc = wave_sum(acc);
             if (lane == 0) p.jumps[((int64_t)traj * S + r) * S + s] = acc;
         }
-    if (lane != 0) return;
+    if (lane != 0 || !p.stay_part) return;      // (no stay_part: the jumps alone, gauss_dwelllen.cpp)
     const int ntile = (T + kDwellTile - 1) / kDwellTile;
     for (int s = 0; s < S; ++s) {
         double acc = 0.0;

@@ -24,6 +24,10 @@ segment by segment against the backward tables of the dwell-time recursion.
 
 `exact_dwell_sensitivities` (bild_gauss_dwell_sensitivities) is the gradient of `exact_dwell`'s evidence
 with respect to model parameters; `GenericGaussianModel.fit_dwell` fits a model, and a Markov prior with it, on that gradient.
+
+`exact_dwell_lengths` (bild_gauss_dwell_lengths) is the gradient of that evidence with respect to the
+prior's own length tables: the expected number of segments of every length; `fit_dwell_prior` fits the dwell-time distributions
+themselves by EM on those counts, in the discrete-hazard parametrisation of `DwellPrior.from_hazard`.
 """
 import math
 import warnings
@@ -628,6 +632,47 @@ class DwellPrior:
             log_init = np.log(init)
         return cls(log_init, log_jump, surv + log_leave[:, None], surv)
 
+    @classmethod
+    def from_hazard(cls, hazard, jump, init=None):
+        """
+        The prior whose dwell times have the discrete hazard h_s(l) = P(a segment in s ends after l frames | it reached l):
+
+            log_surv[s][l] = sum_{m < l} log(1 - h_s(m))   (0 at l = 1),   log_dwell[s][l] = log_surv[s][l] + log h_s(l)
+
+        hazard : (S, L), entries in [0, 1]; column l - 1 is length l.  A hazard of 1 at l admits no longer segment.
+        jump : (S, S) with a zero diagonal; row s is the distribution of the state that follows s, or all zero for a state
+            that never leaves, whose hazard must then be 0 everywhere
+        init : (S,) distribution of the first state, uniform where None
+
+        A constant hazard 1 - P_ss with jump P_ss' / (1 - P_ss) gives `DwellPrior.markov`'s tables.  The prior is normalised
+        over the profiles of every T <= L.  Anything else raises ValueError.
+        """
+        hazard = np.array(hazard, dtype=np.float64)
+        jump = np.array(jump, dtype=np.float64)
+        if hazard.ndim != 2 or hazard.shape[1] < 1:
+            raise ValueError(f"hazard has shape {hazard.shape}; (S, L) with L >= 1 expected")
+        S = hazard.shape[0]
+        if not np.all(np.isfinite(hazard)) or np.any(hazard < 0) or np.any(hazard > 1):
+            raise ValueError("hazard must have finite entries in [0, 1]")
+        if jump.shape != (S, S):
+            raise ValueError(f"jump has shape {jump.shape}; ({S}, {S}) expected")
+        if not np.all(np.isfinite(jump)) or np.any(jump < 0) or np.any(np.diag(jump) != 0):
+            raise ValueError("jump must be finite and non-negative with a zero diagonal")
+        rows = jump.sum(axis=1)
+        never = np.all(jump == 0, axis=1)
+        if np.any(~never & (np.abs(rows - 1) > 1e-9)):
+            raise ValueError("every row of jump must sum to 1 or be all zero")
+        if np.any(hazard[never] > 0):
+            raise ValueError("a state whose row of jump is all zero never leaves: its hazard must be 0")
+        init = np.full(S, 1.0 / S) if init is None else np.asarray(init, dtype=np.float64)
+        if init.shape != (S,) or not np.all(np.isfinite(init)) or np.any(init < 0) or abs(init.sum() - 1) > 1e-9:
+            raise ValueError(f"init must be a distribution over the {S} states")
+        with np.errstate(divide='ignore'):
+            # (the running sum in extended precision: the rounding of L additions stays below that of one)
+            stay = np.log1p(-hazard).astype(np.longdouble)
+            surv = np.concatenate([np.zeros((S, 1)), np.cumsum(stay, axis=1)[:, :-1].astype(np.float64)], axis=1)
+            return cls(np.log(init), np.where(jump > 0, np.log(jump), -np.inf), surv + np.log(hazard), surv)
+
     def log_prob(self, profile):
         """ log prior of an expanded profile (a `Loopingprofile` or an integer array); host only """
         states = np.asarray(profile[:], dtype=int)
@@ -1069,3 +1114,258 @@ def exact_dwell_sensitivities(trajs, model, prior, dmsd=None, dmsd_inf=None, dme
                                          P=P, omit=nan == 'omit', fisher=fisher, scratch_bytes=scratch_bytes, **given)
     return DwellSensitivities(log_evidence=res['logev'], n_nan_windows=res['n_nan_windows'], grad=res['grad'],
                               expected_logL=res['exp_logl'], fisher=res['fisher'])
+
+
+# ---------------------------------------------------------------- expected segment lengths and a fit of the dwell-time prior (section 24)
+
+class DwellLengthCounts:
+    """
+    `exact_dwell_lengths` of one trajectory of T frames: the derivatives of `log_evidence` with respect to the prior's logs,
+    which are posterior expected counts.
+
+    traj, model, prior, nan : as given
+    log_evidence, n_nan_windows, expected_jumps (S, S) : `exact_dwell`'s numbers, bit for bit
+    expected_init : (S,) P(theta_0 = s | data)
+    expected_dwell : (S, T); column l - 1 is the expected number of completed segments in state s of l frames (0 at l = T)
+    expected_censored : (S, T); column l - 1 is the probability that the last, right-censored segment is in s with l frames
+
+    Under nan='propagate' a trajectory with `n_nan_windows` > 0 is NaN in all but `n_nan_windows`; a trajectory without a
+    profile of positive weight has `log_evidence` -inf and NaN counts.
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'log_evidence', 'n_nan_windows', 'expected_jumps', 'expected_init',
+                 'expected_dwell', 'expected_censored')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return f"DwellLengthCounts(T={len(self.traj)}, log_evidence={self.log_evidence!r}, n_nan_windows={self.n_nan_windows})"
+
+    def lifetime_pmf(self, state):
+        """
+        (T,) `expected_dwell[state]` over its sum: the exact posterior mean of the histogram of the completed lifetimes of
+        `state`, column l - 1 for l frames.  NaN when the sum is 0 (no completed segment has positive weight).
+        """
+        row = self.expected_dwell[state]
+        total = row.sum()
+        return row / total if total > 0 else np.full(len(row), np.nan)
+
+
+def exact_dwell_lengths(trajs, model, prior, nan='propagate', scratch_bytes=0):
+    """
+    The exact posterior expected segment-length counts of a `GenericGaussianModel` under a dwell-time prior: how many completed
+    segments of each length every state has, and where the last, censored one stands (bild_gauss_dwell_lengths; DESIGN.md
+    section 24).  They are the derivatives of `exact_dwell`'s evidence with respect to `prior.log_dwell` and
+    `prior.log_surv`, and the E-step of `fit_dwell_prior`.  No draws, no histogram noise.
+
+    trajs, model, prior, nan, scratch_bytes : as for `exact_dwell`; a list gives a list of results from ONE device call
+
+    Every refusal is `exact_dwell`'s and is raised before the trajectories are uploaded.  Returns `DwellLengthCounts` or a list
+    of them.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    if not items:
+        return []
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_dwell_lengths(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
+                                   omit=nan == 'omit', scratch_bytes=scratch_bytes)
+    out = [DwellLengthCounts(traj=t, model=model, prior=prior, nan=nan, log_evidence=float(res['logev'][j]),
+                             n_nan_windows=int(res['n_nan_windows'][j]), expected_jumps=res['exp_jumps'][j].copy(),
+                             expected_init=res['exp_init'][j].copy(), expected_dwell=res['exp_dwell'][j, :, :len(t)].copy(),
+                             expected_censored=res['exp_cens'][j, :, :len(t)].copy())
+           for j, t in enumerate(items)]
+    return out[0] if single else out
+
+
+def _hazard_edges(edges, n):
+    """ `fit_dwell_prior`'s edges, checked; None: the powers of two below n (1 alone for n <= 2) """
+    if edges is None:
+        edges = [1]
+        while 2 * edges[-1] < n:
+            edges.append(2 * edges[-1])
+    edges = np.asarray(edges)
+    if edges.ndim != 1 or len(edges) < 1 or not np.issubdtype(edges.dtype, np.integer) or edges[0] != 1 or np.any(np.diff(edges) <= 0):
+        raise ValueError(f"edges = {edges!r}: a strictly increasing integer array that starts at 1")
+    return edges.astype(np.int64)
+
+
+def _hazard_bins(edges, n):
+    """ (n,) the bin of every length 1 ... n: bin j covers [edges[j], edges[j + 1]), the last one is open """
+    return np.searchsorted(edges, np.arange(1, n + 1), side='right') - 1
+
+
+def hazard_m_step(dwell, cens, jumps, first, edges, hazard, jump, init, allowed=None, min_risk=1e-6):
+    """
+    The exact M-step of a dwell-time prior with a piecewise-constant hazard, on expected counts summed over the data set
+    (host only; `fit_dwell_prior` calls it once per iteration):
+
+        h[s][bin] = sum_bin D / sum_bin (D + R),   R_l = sum_{m > l} (D_m + C_m)
+
+    -- the Kaplan-Meier estimator on expected counts: D_l segments end at l, R_l are still running behind l --,
+    jump[s] proportional to jumps[s] over the allowed s', init proportional to first.
+
+    dwell, cens : (S, n) D and C, column l - 1 for length l;  jumps : (S, S);  first : (S,)
+    edges : (n_bins,) the first length of every bin, strictly increasing from 1
+    hazard (S, n_bins), jump (S, S), init (S,) : the current values, which an entry without mass keeps: a bin whose
+        sum (D + R) is below `min_risk`, a row of jumps or a `first` that sums to 0
+    allowed : (S, S) bool, the jumps that exist (None: every off-diagonal one)
+
+    Returns (hazard, jump, init, supported): new arrays and the (S, n_bins) bool of the bins that had `min_risk` at risk.
+    """
+    dwell, cens = np.asarray(dwell, dtype=np.float64), np.asarray(cens, dtype=np.float64)
+    hazard, jump, init = np.array(hazard, dtype=np.float64), np.array(jump, dtype=np.float64), np.array(init, dtype=np.float64)
+    S, n = dwell.shape
+    n_bins = len(edges)
+    both = dwell + cens
+    running = np.concatenate([np.cumsum(both[:, ::-1], axis=1)[:, ::-1][:, 1:], np.zeros((S, 1))], axis=1)      # R_l
+    bins = _hazard_bins(edges, n)
+    ended, risk = np.zeros((S, n_bins)), np.zeros((S, n_bins))
+    for j in range(n_bins):
+        ended[:, j] = dwell[:, bins == j].sum(axis=1)
+        risk[:, j] = ended[:, j] + running[:, bins == j].sum(axis=1)
+    supported = risk >= min_risk
+    hazard[supported] = np.minimum(ended[supported] / risk[supported], 1.0)
+    off = ~np.eye(S, dtype=bool) if allowed is None else np.asarray(allowed, dtype=bool) & ~np.eye(S, dtype=bool)
+    jumps = np.where(off, np.asarray(jumps, dtype=np.float64), 0.0)
+    mass = jumps.sum(axis=1)
+    jump[mass > 0] = jumps[mass > 0] / mass[mass > 0, None]
+    first = np.asarray(first, dtype=np.float64)
+    if first.sum() > 0:
+        init = first / first.sum()
+    return hazard, jump, init, supported
+
+
+class DwellPriorFit:
+    """
+    `fit_dwell_prior`'s result.
+
+    edges : (n_bins,) the first length of every bin of the piecewise-constant hazard; the last bin is open
+    hazard : (S, n_bins) P(a segment in s ends after l frames | it reached l), l in the bin
+    jump : (S, S) the distribution of the state that follows s; init : (S,)
+    log_evidence : the total log evidence of the data set at every iteration's parameters, one entry per device call; the last
+        belongs to these parameters where the fit converged, and to the parameters one M-step before these where it did not
+    n_iter, converged
+    expected_dwell, expected_censored : (S, n) the data-set sums of the last E-step (`DwellLengthCounts`), n the longest trajectory
+    supported : (S, n_bins) bool; False where the last E-step had less than `min_risk` segments at risk in the bin, which
+        therefore kept its value: the data say nothing about it
+    prior(n=None) : the `DwellPrior` with tables for n frames (None: the longest trajectory of the fit)
+
+    No standard errors: the counts are posterior expectations, not observations, and the information of the marginal
+    likelihood is not computed.
+    """
+
+    __slots__ = ('edges', 'hazard', 'jump', 'init', 'log_evidence', 'n_iter', 'converged', 'expected_dwell', 'expected_censored',
+                 'supported')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return f"DwellPriorFit(n_iter={self.n_iter}, converged={self.converged}, edges={self.edges.tolist()}, hazard={self.hazard!r})"
+
+    def prior(self, n=None):
+        n = self.expected_dwell.shape[1] if n is None else n
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"n = {n!r}: a positive integer")
+        return DwellPrior.from_hazard(self.hazard[:, _hazard_bins(self.edges, int(n))], self.jump, self.init)
+
+
+def _hazard_start(model, start, n_bins):
+    """ `fit_dwell_prior`'s start -> (allowed (S, S), hazard (S, n_bins), jump (S, S), init (S,)), checked """
+    S = model.msd.shape[0]
+    allowed = np.asarray(model.transitions, dtype=bool).copy()
+    if allowed.shape != (S, S):
+        raise ValueError(f"model.transitions has shape {allowed.shape}; ({S}, {S}) expected")
+    np.fill_diagonal(allowed, False)
+    leaves = allowed.any(axis=1)
+    even = np.where(allowed, 1.0 / np.maximum(allowed.sum(axis=1), 1)[:, None], 0.0)
+    if start is None:
+        hazard, jump, init = np.where(leaves[:, None], np.full((S, n_bins), 0.1), 0.0), even, np.full(S, 1.0 / S)
+    elif isinstance(start, MarkovPriorFit):
+        P = np.asarray(start.P, dtype=np.float64)
+        if P.shape != (S, S):
+            raise ValueError(f"start.P has shape {P.shape}; ({S}, {S}) expected")
+        off = P - np.diag(np.diag(P))
+        leave = off.sum(axis=1)
+        hazard = np.repeat(leave[:, None], n_bins, axis=1)
+        jump = np.where(leave[:, None] > 0, off / np.where(leave > 0, leave, 1.0)[:, None], 0.0)
+        init = np.array(start.init, dtype=np.float64)
+    elif isinstance(start, tuple) and len(start) == 3:
+        hazard, jump, init = (np.array(a, dtype=np.float64) for a in start)
+    else:
+        raise ValueError("start must be None, a MarkovPriorFit or a (hazard_per_bin, jump, init) tuple")
+    if hazard.shape != (S, n_bins):
+        raise ValueError(f"the start's hazard has shape {hazard.shape}; ({S}, {n_bins}) expected")
+    if jump.shape != (S, S) or init.shape != (S,):
+        raise ValueError(f"the start's jump and init have shapes {jump.shape} and {init.shape}; ({S}, {S}) and ({S},) expected")
+    if np.any((jump > 0) & ~allowed):
+        raise ValueError("start has a positive jump that model.transitions forbids")
+    return allowed, hazard, jump, init
+
+
+def fit_dwell_prior(trajs, model, edges=None, start=None, tol=1e-8, max_iter=500, min_risk=1e-6, nan='propagate'):
+    """
+    Maximum-likelihood dwell-time distributions of a data set: EM over a whole `DwellPrior` in the discrete-hazard
+    parametrisation (`DwellPrior.from_hazard`), the model held fixed.  The hazard of every state is piecewise constant on bins
+    of lengths; the E-step is one `exact_dwell_lengths` device call on a trajectory set that is built once, the M-step is exact
+    and in closed form (`hazard_m_step`: Kaplan-Meier on the expected counts).  `fit_markov_prior` is the case of one bin.
+
+    trajs : a list of trajectories (or one)
+    model : a `GenericGaussianModel` (anything else: TypeError); transitions that `model.transitions` forbids stay 0
+    edges : the first length of every bin, a strictly increasing integer array that starts at 1.  Bin j covers the lengths
+        [edges[j], edges[j + 1]), the last bin is open up to the longest trajectory n; the states share the bins.  None: the
+        doubling edges 1, 2, 4, ... below n.  [1]: the Markov family.
+    start : None -- hazard 0.1 everywhere, jumps spread evenly over the allowed transitions, uniform init; a `MarkovPriorFit`;
+        or a (hazard per bin (S, n_bins), jump (S, S), init (S,)) tuple
+    tol : stop when an M-step moves no bin hazard, jump entry or init entry by more than this
+    max_iter : at most this many device calls
+    min_risk : a bin with fewer expected segments at risk than this keeps its value (see `DwellPriorFit.supported`), and so
+        does a jump row without mass: a partial M-step, so the total log evidence never decreases
+    nan : as for `exact_dwell`; a total evidence that is not finite raises `EvidenceNotFinite`
+
+    A fit that converges returns the parameters of its last E-step, which the M-step would have moved by no more than `tol`:
+    `log_evidence[-1]`, `expected_dwell` and `expected_censored` are then those of `prior()`.  A fit that stops at `max_iter`
+    returns the last M-step's parameters, one step ahead of `log_evidence[-1]`, as `fit_markov_prior` does.
+
+    EM on a hidden semi-Markov model may stop at a local optimum.  No standard errors are reported: the expected counts are
+    not observations, and the information of the marginal likelihood is not computed.  Returns `DwellPriorFit`.
+    """
+    from .gauss import GenericGaussianModel
+    if not isinstance(model, GenericGaussianModel):
+        raise TypeError(f"fit_dwell_prior needs a GenericGaussianModel, whose log-likelihood is a sum of segment terms, not "
+                        f"{type(model).__name__}")
+    single = not isinstance(trajs, (list, tuple))
+    items = [trajs] if single else list(trajs)
+    if not items:
+        raise ValueError("fit_dwell_prior needs at least one trajectory")
+    n = max(len(t) for t in items)
+    edges = _hazard_edges(edges, n)
+    allowed, hazard, jump, init = _hazard_start(model, start, len(edges))
+    if not (tol > 0) or isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1 or not (min_risk > 0):
+        raise ValueError(f"tol = {tol!r} and min_risk = {min_risk!r} must be positive and max_iter = {max_iter!r} a positive integer")
+    bins = _hazard_bins(edges, n)
+    _check_exact_dwell(items, model, DwellPrior.from_hazard(hazard[:, bins], jump, init), nan)
+
+    ts = model.trajset(items[0] if single else items)       # built once: the iterations change the prior, not the tables
+    history, converged = [], False
+    for _ in range(int(max_iter)):
+        prior = DwellPrior.from_hazard(hazard[:, bins], jump, init)
+        res = _lib.gauss_dwell_lengths(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
+                                       omit=nan == 'omit')
+        total = float(np.sum(res['logev']))
+        if not np.isfinite(total):
+            raise EvidenceNotFinite(total)
+        history.append(total)
+        dwell, cens = res['exp_dwell'].sum(axis=0), res['exp_cens'].sum(axis=0)
+        new_hazard, new_jump, new_init, supported = hazard_m_step(dwell, cens, res['exp_jumps'].sum(axis=0), res['exp_init'].sum(axis=0),
+                                                                  edges, hazard, jump, init, allowed=allowed, min_risk=min_risk)
+        step = max(float(np.max(np.abs(new_hazard - hazard))), float(np.max(np.abs(new_jump - jump))), float(np.max(np.abs(new_init - init))))
+        if step <= tol:     # (the step is not taken: the evidence and the counts stay those of the parameters returned)
+            converged = True
+            break
+        hazard, jump, init = new_hazard, new_jump, new_init
+    return DwellPriorFit(edges=edges, hazard=hazard, jump=jump, init=init, log_evidence=np.array(history), n_iter=len(history),
+                         converged=converged, expected_dwell=dwell, expected_censored=cens, supported=supported)

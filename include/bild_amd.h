@@ -1099,6 +1099,39 @@ int bild_gauss_dwell_sensitivities(const bild_gauss_model *m, const bild_gauss_t
                                    const double *log_surv, unsigned flags, int P, const bild_gauss_derivs *dm,
                                    int64_t scratch_bytes, bild_dwellsens_out *out);
 
+/* ---------------------------------------------------------------- expected segment lengths under a dwell-time prior ----
+ * GenericGaussianModel only, at most 4 states.  The derivatives of logev of bild_gauss_dwell_evidence
+ * (same tables, same NaN flag, same refusals) with respect to the prior's own logs: expected counts, the E-step of a fit of
+ * the whole dwell-time prior.  With Q(a, b, s) the posterior probability of the segment [a, b) in state s (the block above),
+ * per trajectory of T frames:
+ *   logev, n_nan_windows, exp_jumps   as bild_gauss_dwell_evidence gives them, bit for bit: the same kernels on the same tables
+ *   exp_init       S: I[s] = sum_{b = 1 .. T} Q(0, b, s) = P(theta_0 = s | data)                 (d logev / d log_init[s])
+ *   exp_dwell      S x T_max, length l at column l - 1: D[s][l] = sum_{a = 0 .. T - l - 1} Q(a, a + l, s), the expected number
+ *                  of completed segments in state s of l frames, l = 1 .. T - 1                  (d logev / d log_dwell[s][l])
+ *   exp_cens       S x T_max, length l at column l - 1: C[s][l] = Q(T - l, T, s), the probability that the last, right-censored
+ *                  segment is in state s and has l frames, l = 1 .. T                             (d logev / d log_surv[s][l])
+ * Columns behind the trajectory's T are 0, and so is exp_dwell at l = T.  Every exponent is clamped at 0, as in the block
+ * above; a NaN window, a start that no profile reaches and a tail of weight 0 add nothing.  Sums of non-negative terms:
+ * sum_l D[s][l] = sum_s' exp_jumps[s][s'], sum_{s, l} C = 1, sum_l (l - 1) (D + C)[s][l] = exp_stay[s] and
+ * sum_{s, l} l (D + C)[s][l] = T up to rounding.  flags = 0 (BILD_DWELL_NAN_PROPAGATE): a trajectory with n_nan_windows > 0
+ * has NaN in logev and in every count (columns l <= T).  BILD_DWELL_NAN_OMIT: the skipped windows weigh 0.  A trajectory without
+ * a profile of positive weight has logev -inf and NaN in every count.  The start frames a are summed in blocks of 64 frames
+ * of the trajectory, ascending inside a block, the blocks in order: no atomics, fixed summation orders that depend on the
+ * trajectory alone, so results are bit-identical across calls, the order of the set, a trajectory alone or in a batch, and
+ * scratch_bytes (chunks of whole trajectories; 0: at most 1 GiB and a third of the free device memory).  The marginals and
+ * the MAP profile of bild_gauss_dwell_evidence are not computed.  Plain launches on the set's stream.  Synchronous. */
+typedef struct bild_dwell_lengths_out {
+    double *logev;                          /* n_traj */
+    int64_t *n_nan_windows;                 /* n_traj */
+    double *exp_jumps;                      /* n_traj x S x S */
+    double *exp_init;                       /* n_traj x S */
+    double *exp_dwell, *exp_cens;           /* n_traj x S x T_max each */
+} bild_dwell_lengths_out;                   /* every pointer may be NULL: not written */
+
+int bild_gauss_dwell_lengths(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
+                             const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, unsigned flags,
+                             int64_t scratch_bytes, bild_dwell_lengths_out *out);
+
 #ifdef __cplusplus
 }
 #endif
