@@ -963,7 +963,12 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
         };
         // one frame t >= 1: predict (pyx:206-241), masked update (pyx:244-248)
         auto frame = [&](const double (&xv)[CPL], double probe) {
-            if (ROW && kLean) s2_now = row_const[0];
+            if (ROW && kLean) {
+                // (issued HERE: the scheduler sinks the read to just in front of the S sum it starts, and every frame then waits
+                // for LDS between its two dot products -- in front of the predict the latency hides behind ten FMAs)
+                s2_now = row_const[0];
+                __builtin_amdgcn_sched_barrier(0);
+            }
             if constexpr (PAIR) {
 #pragma unroll
                 for (int k = 0; k < NP / 2; ++k) colh[k] = fma(L.v[0][k], colh[k], sgd[k]);
@@ -1346,6 +1351,31 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
             const int kTailMargin = p.tail_margin; // frames beyond the table's own transient before the next switch may come (8)
             const bool tails = JUMP && p.tail_g != nullptr && !building_transients;
             bool near = true;
+            // (the listed frame loop: every load of the look in flight, then ONE wait, as in `sandwich` -- the compiler's own order
+            // is load, wait, compare, five times over, for the 80 bytes of one column.  With them the two running sums a look that
+            // converges adds afterwards: the frame it goes on at is known before the comparison.)
+            constexpr bool kBatchLook = kLean && CPL == 1;
+            double look[kBatchLook ? NP : 1], look_L = 0.0, look_L2 = 0.0;
+            if constexpr (kBatchLook) {
+                if (hasImg[0]) {
+                    if constexpr (PAIR) {
+#pragma unroll
+                        for (int k = 0; k < NP / 2; ++k) look[k] = rec[cidx[0] * NP + 2 * k + odd];
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < NP; i += 2) {
+                            const double2 r2 = *reinterpret_cast<const double2 *>(rec + cidx[0] * NP + i);
+                            look[i] = r2.x;
+                            look[i + 1] = r2.y;
+                        }
+                    }
+                }
+                if (!building_transients) {
+                    look_L = rec[kRecL];
+                    look_L2 = record((next_start < T ? next_start : T) - 1)[kRecL];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int q = 0; q < CPL; ++q) {
                 if (!hasImg[q]) continue;
@@ -1360,7 +1390,9 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                     double devh = 0.0, refh = ref;
 #pragma unroll
                     for (int k = 0; k < NP / 2; ++k) {
-                        const double rk = rec[cidx[q] * NP + 2 * k + odd];
+                        double rk;
+                        if constexpr (kBatchLook) rk = look[k];
+                        else rk = rec[cidx[q] * NP + 2 * k + odd];
                         devh = fmax(devh, fabs(colh[k] - rk));
                         refh = fmax(refh, fabs(rk));
                     }
@@ -1372,7 +1404,9 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                 } else {
 #pragma unroll
                     for (int i = 0; i < NP; i += 2) {
-                        const double2 r2 = *reinterpret_cast<const double2 *>(rec + cidx[q] * NP + i);
+                        double2 r2;
+                        if constexpr (kBatchLook) r2 = make_double2(look[i], look[i + 1]);
+                        else r2 = *reinterpret_cast<const double2 *>(rec + cidx[q] * NP + i);
                         dev = fmax(dev, fmax(fabs(col.v[q][i] - r2.x), fabs(col.v[q][i + 1] - r2.y)));
                         ref = fmax(ref, fmax(fabs(r2.x), fabs(r2.y)));
                     }
@@ -1461,7 +1495,8 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                 // (the lean loop has asked for frame t + 1 already, the other one has not)
                 const int t_ptr = kLean ? t + 2 : t + 1;
                 const int t2 = next_start < T ? next_start : T;
-                extra += record(t2 - 1)[kRecL] - rec[kRecL];
+                if constexpr (kBatchLook) extra += look_L2 - look_L;
+                else extra += record(t2 - 1)[kRecL] - rec[kRecL];
                 t = t2;
                 land();
                 if (t < T) {
