@@ -219,8 +219,6 @@ struct Geometry {
 
 // doubles of LDS one group needs: image of X*[C|M], NP+kDMax columns of NP rows
 constexpr int group_image_doubles(int NP) { return (NP + kDMax) * NP; }
-// LDS layout of the vector kernels, in doubles: [matrix tables (tab_doubles)] [per state: lam | wq | sig (3 NP each)]
-// [per group: product image] [per group: the task's segment list, kSegLds (start, state) pairs]
 constexpr int kFrameCounters = 256; // words of the frames-run counter (KParams::frames_run), summed by the host
 constexpr int kSegLds = 16;
 constexpr int kRowConsts = 2; // per-task constants the frame loop reads from LDS instead of holding (or spilling) registers: s2
@@ -228,6 +226,23 @@ constexpr int group_seg_doubles() { return kSegLds + kRowConsts; } // 2 * kSegLd
 constexpr int state_header_doubles(int NP) { return 3 * NP; }
 // optional (KParams::walk_lds): the task's table entries, fetched for all its switches at once -- 3 doubles per switch
 constexpr int kWalkDoubles = 3 * kSegLds;
+// THE LDS layout of a workgroup of the vector kernels: where each area begins, in doubles from the LDS base, for a workgroup of
+// `groups` = W * (64 / G) groups (rows).  The frame loop (logl_body.h), the one-launch kernel and its walk (kernels.hip) and the
+// host's size computation (model.cpp: lds_bytes; launch.cpp) all take their offsets from here.
+//   [matrix tables: tab_doubles] [per state: lam | wq | sig] [per group: product image] [per group: segment list, kSegLds (start,
+//   state) pairs, and the row constants] [per group: walk plan -- with KParams::walk_lds] [OneHand -- the one-launch path]
+struct LdsLayout {
+    int groups, hdr0, img0, seg0, walk0, hand0;
+    constexpr LdsLayout(int NP, int groups_, int tab_doubles, int S)
+        : groups(groups_), hdr0(tab_doubles), img0(hdr0 + S * state_header_doubles(NP)), seg0(img0 + groups_ * group_image_doubles(NP)),
+          walk0(seg0 + groups_ * group_seg_doubles()), hand0(walk0 + groups_ * kWalkDoubles)
+    {
+    }
+    // bytes of a launch without walk plans, and what the plans / the hand-off record add
+    constexpr size_t frame_bytes() const { return (size_t)walk0 * sizeof(double); }
+    constexpr size_t walk_bytes() const { return (size_t)(hand0 - walk0) * sizeof(double); }
+    static constexpr size_t hand_bytes() { return sizeof(OneHand); }
+};
 
 // host-callable launchers implemented in kernels.hip
 // (ev_start / ev_stop: hipEvent_t attached to the dispatch of a timed launch, or null)

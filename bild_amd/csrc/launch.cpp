@@ -4,6 +4,7 @@
 #include <queue>
 #include <utility>
 
+#include "chain_work.h"
 #include "likelihood.h"
 
 namespace {
@@ -81,7 +82,7 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
                             !(flags & BILD_NO_SPLIT) && ntasks <= (int64_t)INT_MAX;
     // room for the walk plan (the table entries of all switches of a task, fetched at once) where it does not cost occupancy
     // (a CU holds OCC waves per SIMD = 4 OCC / W workgroups of a geometry, and 160 KiB of LDS for them)
-    auto walk_bytes = [](const Geometry &g) { return (size_t)g.W * (64 / g.G) * kWalkDoubles * sizeof(double); };
+    auto walk_bytes = [](const Geometry &g) { return LdsLayout(g.NP, g.W * (64 / g.G), 0, 0).walk_bytes(); };
     auto walk_fits = [&](const Geometry &g, size_t lds) {
         return K1 <= kSegLds && !config().no_walk_plan &&
                lds + walk_bytes(g) <= (size_t)160 * 1024 / (size_t)std::max(1, (4 * g.OCC + g.W - 1) / g.W);
@@ -200,7 +201,7 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
     const int64_t one_grid = std::min<int64_t>(ntasks, 256 * (int64_t)std::max(geom.OCC, 1));
     const bool one = split && frame_loop && fam == kVector && geom.id == 23 && geom.lay == 3 && K1 <= kOneLaunchMaxK1 && ntasks >= 1 &&
                      ntasks <= kOneLaunchMaxTasks && (ntasks + one_grid - 1) / one_grid <= kOneSlice && !config().no_one_launch &&
-                     lds + sizeof(OneHand) <= (size_t)160 * 1024 / (size_t)std::max(1, (4 * geom.OCC + geom.W - 1) / geom.W);
+                     lds + LdsLayout::hand_bytes() <= (size_t)160 * 1024 / (size_t)std::max(1, (4 * geom.OCC + geom.W - 1) / geom.W);
 
     // What this call allocates and creates for itself, released by whatever path it returns: the frees are stream-ordered
     // behind everything the call enqueued, the events are destroyed unless they were handed to the timing lists.
@@ -363,7 +364,7 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
     const bool ride = fam == kVector;
     if (timing && !ride) HIP_TRY(hipEventRecord(own.e0, st));
     int lrc = !frame_loop          ? 0
-              : one                ? launch_logl_one(geom, p, w, grid, lds + sizeof(OneHand), (void *)st, timing ? (void *)own.e0 : nullptr,
+              : one                ? launch_logl_one(geom, p, w, grid, lds + LdsLayout::hand_bytes(), (void *)st, timing ? (void *)own.e0 : nullptr,
                                                      timing ? (void *)own.e1 : nullptr)
               : fam == kWide       ? launch_logl_wide(m.NP, p, grid, (void *)st)
               : fam == kModalTiles ? launch_logl_modal_mfma(m.NPm[kModal], p, (void *)st)
@@ -432,29 +433,15 @@ bool schedule(const bild_model &m, const bild_trajset &ts, int64_t n, int K1, co
             t0 = t0 < 1 ? 1 : (t0 > T ? T : t0);
             w = T - t0;
         } else {
-            // Frames the candidate will run itself, estimated from its switch frames alone: a switch whose segment is at
-            // least m_typ frames long (the table's typical frames-to-convergence) comes out of the transient table, unless a
-            // run is in progress, which then ends m_typ frames behind it; shorter segments chain into one run.  (Boundaries
-            // that switch nothing are rare and only blur the estimate.)
-            int run_from = -1, links = 0;
+            // Frames the candidate will run itself, estimated from its switch frames alone (chain_work.h), over the list as
+            // given.  (Boundaries that switch nothing are rare and only blur the estimate.)
+            ChainWork cw{m_typ, pairs};
             for (int i = 1; i < K1; ++i) {
                 const int t = a[i];
                 if (t >= T) break;
-                const int gap = ((i + 1 < K1 && a[i + 1] < T) ? a[i + 1] : T) - t;
-                if (run_from < 0) {
-                    if (gap < m_typ) {
-                        run_from = t;
-                        links = 1;
-                    }
-                } else {
-                    ++links;
-                    if (gap >= m_typ) {
-                        if (!(pairs && links == 2)) w += t + m_typ - run_from; // two switches: out of the pair table
-                        run_from = -1;
-                    }
-                }
+                cw.add(t, ((i + 1 < K1 && a[i + 1] < T) ? a[i + 1] : T) - t);
             }
-            if (run_from >= 0 && !(links == 1 || (pairs && links == 2))) w += T - run_from;
+            w = cw.finish(T);
             w = w > Tmax ? Tmax : w;
         }
         w = w < 0 ? 0 : w; // (a row of decreasing starts can make the estimate negative; host entries reject such rows beforehand)

@@ -335,10 +335,8 @@ namespace bild {
 
 size_t lds_bytes(const bild_model &m, const Geometry &geom, int mode)
 {
-    // matrix tables (dense: B_s, Sig_s; modal: basis changes R) + per-group product images
-    const size_t groups = (size_t)geom.W * (64 / geom.G);
-    const size_t image = (size_t)group_image_doubles(geom.NP) + group_seg_doubles();
-    return (m.blob_tab[mode].size() + (size_t)m.S * state_header_doubles(geom.NP) + groups * image) * sizeof(double);
+    // matrix tables (dense: B_s, Sig_s; modal: basis changes R), state headers, per-group product images and segment lists
+    return LdsLayout(geom.NP, geom.W * (64 / geom.G), (int)m.blob_tab[mode].size(), m.S).frame_bytes();
 }
 
 int ensure_device(const bild_model &m)

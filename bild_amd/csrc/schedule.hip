@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include "chain_work.h"
 #include "common.h"
 
 namespace bild {
@@ -24,27 +25,14 @@ __global__ void __launch_bounds__(256) work_kernel(const int32_t *__restrict__ s
     if (r < n) {
         const int T = trajs[traj_id ? traj_id[r] : 0].T;
         const int32_t *a = seg_start + r * K1;
-        // (as api.cpp: schedule) a chain = switches less than m_typ frames apart; one switch, or two with the pair table,
-        // come out of the tables
-        int run_from = -1, links = 0;
+        // (chain_work.h, over the list as given)
+        ChainWork cw{m_typ, pairs != 0};
         for (int i = 1; i < K1; ++i) {
             const int t = a[i];
             if (t >= T) break;
-            const int gap = ((i + 1 < K1 && a[i + 1] < T) ? a[i + 1] : T) - t;
-            if (run_from < 0) {
-                if (gap < m_typ) {
-                    run_from = t;
-                    links = 1;
-                }
-            } else {
-                ++links;
-                if (gap >= m_typ) {
-                    if (!(pairs && links == 2)) w += t + m_typ - run_from;
-                    run_from = -1;
-                }
-            }
+            cw.add(t, ((i + 1 < K1 && a[i + 1] < T) ? a[i + 1] : T) - t);
         }
-        if (run_from >= 0 && !(links == 1 || (pairs && links == 2))) w += T - run_from;
+        w = cw.finish(T);
         w = w > Tmax ? Tmax : (w < 0 ? 0 : w);
         keys[r] = (unsigned)(Tmax - w); // ascending keys = descending work
         idx[r] = (int32_t)r;

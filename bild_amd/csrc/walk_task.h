@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
+#include "chain_work.h"
 #include "common.h"
 
 namespace bild {
@@ -238,32 +239,14 @@ __device__ __forceinline__ int walk_task(const WalkParams &p, const int64_t task
     }
 
     // ---- a chain the tables do not cover: hand the task to the frame loop, in the bucket of its expected work ----------
-    // (the estimate of the host scheduler, api.cpp: schedule -- chains of switches less than m_typ frames apart)
-    int w = 0;
-    {
-        int run_from = -1, links = 0;
-        const int mt = p.m_typ;
-        const bool pairs = p.trans2 != nullptr;
+    // (chain_work.h, over the entries of the `keep` mask)
+    ChainWork cw{p.m_typ, p.trans2 != nullptr};
 #pragma unroll
-        for (int i = 1; i < KMAX; ++i) {
-            if (!(keep & (1u << i))) continue;
-            const int t1 = a[i];
-            const int gap = (n2[i] < T ? n2[i] : T) - t1;
-            if (run_from < 0) {
-                if (gap < mt) {
-                    run_from = t1;
-                    links = 1;
-                }
-            } else {
-                ++links;
-                if (gap >= mt) {
-                    if (!(pairs && links == 2)) w += t1 + mt - run_from;
-                    run_from = -1;
-                }
-            }
-        }
-        if (run_from >= 0 && !(links == 1 || (pairs && links == 2))) w += T - run_from;
+    for (int i = 1; i < KMAX; ++i) {
+        if (!(keep & (1u << i))) continue;
+        cw.add(a[i], (n2[i] < T ? n2[i] : T) - a[i]);
     }
+    const int w = cw.finish(T);
     if (p.no_lists) { // (cannot happen: the host checked the tables entry by entry -- a visible NaN rather than a stale result if it did)
         p.out[task] = __longlong_as_double(0x7ff8000000000000ll);
         return -1;
