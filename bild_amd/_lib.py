@@ -273,6 +273,12 @@ def i32(a):
 _addressof, _from_buffer = ctypes.addressof, ctypes.c_char.from_buffer
 
 
+def _traj_block(trajs):
+    """ a list of (T, d) arrays -> (T (n,) int32, their frames in one (sum T, d) float64 block) """
+    arrs = [f64(t) for t in trajs]
+    return i32([a.shape[0] for a in arrs]), f64(np.concatenate(arrs, axis=0))
+
+
 def aptr(a):
     """
     address of a C-contiguous array of any element type; the CALLER keeps the array alive across the call (no temporaries
@@ -335,8 +341,7 @@ class TrajSetHandle:
         for a in arrs:
             if a.ndim != 2 or a.shape[1] != model.d:
                 raise AssertionError(f"trajectory shape {a.shape} does not match model dimension d={model.d}")
-        self.T = i32([a.shape[0] for a in arrs])
-        x = f64(np.concatenate(arrs, axis=0))
+        self.T, x = _traj_block(arrs)
         err = f64(loc_errs).reshape(len(arrs), model.d)
         self.n_traj = len(arrs)
         self._h = _vp()
@@ -379,8 +384,7 @@ class GaussTrajSetHandle:
         for a in arrs:
             if a.ndim != 2 or a.shape[1] != model.d:
                 raise AssertionError(f"trajectory shape {a.shape} does not match model dimension d={model.d}")
-        self.T = i32([a.shape[0] for a in arrs])
-        x = f64(np.concatenate(arrs, axis=0))
+        self.T, x = _traj_block(arrs)
         self.n_traj = len(arrs)
         self._h = _vp()
         check(lib().bild_gauss_trajset_create(model._h, self.n_traj, iptr(self.T), dptr(x), ctypes.byref(self._h)))
@@ -674,6 +678,18 @@ class GaussDerivs(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in ('dmsd', 'dmsd_inf', 'dmean')]
 
 
+def _gauss_derivs(model, P, dmsd, dmsd_inf, dmean):
+    """ dmsd (P, S, d, Tmax + 1), dmsd_inf and dmean (P, S, d), None = zero -> (GaussDerivs, the arrays it points into) """
+    S, d, L1 = model.S, model.d, model.Tmax + 1
+    keep = {}
+    for name, a, shape in (('dmsd', dmsd, (P, S, d, L1)), ('dmsd_inf', dmsd_inf, (P, S, d)), ('dmean', dmean, (P, S, d))):
+        if a is not None:
+            a = f64(a)
+            assert a.shape == shape, f"{name} has shape {a.shape}, expected {shape}"
+            keep[name] = a
+    return GaussDerivs(**{k: aptr(a) if a.size else None for k, a in keep.items()}), keep
+
+
 def gauss_logl_sensitivities(model, trajs, seg_start, seg_state, traj_id=None, dmsd=None, dmsd_inf=None, dmean=None, P=0,
                              fisher=True, scratch_bytes=0):
     """
@@ -686,21 +702,12 @@ def gauss_logl_sensitivities(model, trajs, seg_start, seg_state, traj_id=None, d
     assert seg_state.shape == (n, K1)
     tid = None if traj_id is None else i32(traj_id)
     assert tid is None or tid.shape == (n,)
-    arrs = [f64(t) for t in trajs]
-    T = i32([a.shape[0] for a in arrs])
-    x = f64(np.concatenate(arrs, axis=0))
-    S, d, L1 = model.S, model.d, model.Tmax + 1
-    keep = {}
-    for name, a, shape in (('dmsd', dmsd, (P, S, d, L1)), ('dmsd_inf', dmsd_inf, (P, S, d)), ('dmean', dmean, (P, S, d))):
-        if a is not None:
-            a = f64(a)
-            assert a.shape == shape, f"{name} has shape {a.shape}, expected {shape}"
-            keep[name] = a
-    spec = GaussDerivs(**{k: aptr(a) if a.size else None for k, a in keep.items()})
+    T, x = _traj_block(trajs)
+    spec, keep = _gauss_derivs(model, P, dmsd, dmsd_inf, dmean)
     logl = np.empty(n, dtype=np.float64)
     g = np.empty((n, P), dtype=np.float64)
     F = np.empty((n, P, P), dtype=np.float64) if fisher else None
-    check(lib().bild_gauss_logl_sensitivities(model._h, len(arrs), iptr(T), dptr(x), n, K1, iptr(seg_start), iptr(seg_state),
+    check(lib().bild_gauss_logl_sensitivities(model._h, len(T), iptr(T), dptr(x), n, K1, iptr(seg_start), iptr(seg_state),
                                               iptr(tid), int(P), ctypes.byref(spec), dptr(logl),
                                               dptr(g) if g.size else None, dptr(F) if F is not None and F.size else None,
                                               int(scratch_bytes)))
@@ -722,9 +729,7 @@ def gauss_kalman_segments(model, trajs, seg_start, seg_state, traj_id=None, outp
     assert seg_state.shape == (n, K1)
     tid = None if traj_id is None else i32(traj_id)
     assert tid is None or tid.shape == (n,)
-    arrs = [f64(t) for t in trajs]
-    T = i32([a.shape[0] for a in arrs])
-    x = f64(np.concatenate(arrs, axis=0))
+    T, x = _traj_block(trajs)
     if T_max is None:
         T_max = int(np.max(T))
     res = {}
@@ -734,7 +739,7 @@ def gauss_kalman_segments(model, trajs, seg_start, seg_state, traj_id=None, outp
             raise ValueError(f"unknown output {name!r}")
         res[name] = np.empty((n, T_max, model.d), dtype=np.float64)
         setattr(spec, name, aptr(res[name]) if res[name].size else None)
-    check(lib().bild_gauss_kalman_segments(model._h, len(arrs), iptr(T), dptr(x), n, K1, iptr(seg_start), iptr(seg_state),
+    check(lib().bild_gauss_kalman_segments(model._h, len(T), iptr(T), dptr(x), n, K1, iptr(seg_start), iptr(seg_state),
                                            iptr(tid), ctypes.byref(spec), int(scratch_bytes)))
     return res
 
@@ -750,12 +755,10 @@ def gauss_kalman_mixture(model, trajs, seg_start, seg_state, log_weights, traj_i
     lw = f64(log_weights).reshape(-1)
     assert lw.shape == (n,)
     tid = None if traj_id is None else i32(traj_id)
-    arrs = [f64(t) for t in trajs]
-    T = i32([a.shape[0] for a in arrs])
-    x = f64(np.concatenate(arrs, axis=0))
-    mean = np.empty((len(arrs), int(np.max(T)), model.d), dtype=np.float64)
+    T, x = _traj_block(trajs)
+    mean = np.empty((len(T), int(np.max(T)), model.d), dtype=np.float64)
     var = np.empty_like(mean)
-    check(lib().bild_gauss_kalman_mixture(model._h, len(arrs), iptr(T), dptr(x), n, K1, iptr(seg_start), iptr(seg_state),
+    check(lib().bild_gauss_kalman_mixture(model._h, len(T), iptr(T), dptr(x), n, K1, iptr(seg_start), iptr(seg_state),
                                           iptr(tid), dptr(lw), dptr(mean), dptr(var), int(scratch_bytes)))
     return mean, var
 
@@ -1338,21 +1341,13 @@ def gauss_segment_sensitivities(model, ts, trajs, k_max, transitions, log_k_prio
     """
     tr = _transitions_u8(transitions, model.S)
     n, K = ts.n_traj, int(k_max) + 1
-    arrs = [f64(t) for t in trajs]
-    assert len(arrs) == n and all(len(a) == T for a, T in zip(arrs, ts.T))
-    x = f64(np.concatenate(arrs, axis=0))
+    T, x = _traj_block(trajs)
+    assert np.array_equal(T, ts.T)
     prior = None
     if log_k_prior is not None:
         prior = f64(log_k_prior)
         assert prior.shape == (n, K)
-    S, d, L1 = model.S, model.d, model.Tmax + 1
-    keep = {}
-    for name, a, shape in (('dmsd', dmsd, (P, S, d, L1)), ('dmsd_inf', dmsd_inf, (P, S, d)), ('dmean', dmean, (P, S, d))):
-        if a is not None:
-            a = f64(a)
-            assert a.shape == shape, f"{name} has shape {a.shape}, expected {shape}"
-            keep[name] = a
-    derivs = GaussDerivs(**{k: aptr(a) if a.size else None for k, a in keep.items()})
+    derivs, keep = _gauss_derivs(model, P, dmsd, dmsd_inf, dmean)
     res = {'logev': np.empty((n, K)), 'log_marginal': np.empty(n), 'k_post': np.empty((n, K)), 'grad': np.empty((n, P)),
            'exp_logl': np.empty(n), 'fisher': np.empty((n, P, P)) if fisher else None}
     spec = SegsensOut(**{name: (aptr(a) if a is not None and a.size else None) for name, a in res.items()})
@@ -1370,6 +1365,15 @@ class DwellOut(ctypes.Structure):
 DWELL_NAN_PROPAGATE, DWELL_NAN_OMIT = 0, 1
 
 
+def _dwell_tables(model, log_init, log_jump, log_dwell, log_surv):
+    """ the four tables of a dwell-time prior as float64, shapes checked -> ((log_init, log_jump, log_dwell, log_surv), L) """
+    S = model.S
+    log_init, log_jump, log_dwell, log_surv = f64(log_init), f64(log_jump), f64(log_dwell), f64(log_surv)
+    L = log_dwell.shape[1]
+    assert log_init.shape == (S,) and log_jump.shape == (S, S) and log_dwell.shape == (S, L) and log_surv.shape == (S, L)
+    return (log_init, log_jump, log_dwell, log_surv), L
+
+
 def gauss_dwell_evidence(model, ts, log_init, log_jump, log_dwell, log_surv, marginals=True, omit=False, scratch_bytes=0):
     """
     exact inference under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_evidence): a dict of logev,
@@ -1377,9 +1381,7 @@ def gauss_dwell_evidence(model, ts, log_init, log_jump, log_dwell, log_surv, mar
     (n_traj, S, T_max), exp_jumps (n_traj, S, S) and exp_stay (n_traj, S) (None without); T_max the set's longest trajectory
     """
     S = model.S
-    log_init, log_jump, log_dwell, log_surv = f64(log_init), f64(log_jump), f64(log_dwell), f64(log_surv)
-    L = log_dwell.shape[1]
-    assert log_init.shape == (S,) and log_jump.shape == (S, S) and log_dwell.shape == (S, L) and log_surv.shape == (S, L)
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
     n = ts.n_traj
     T_max = int(np.max(ts.T))
     res = {'logev': np.empty(n), 'map_logjoint': np.empty(n), 'map_states': np.empty((n, T_max), dtype=np.uint8),
@@ -1404,21 +1406,11 @@ def gauss_dwell_sensitivities(model, ts, trajs, log_init, log_jump, log_dwell, l
     `gauss_logl_sensitivities`.  A dict of logev, exp_logl (n_traj,), n_nan_windows (n_traj,) int64, grad (n_traj, P) and
     fisher (n_traj, P, P) or None
     """
-    S, d, L1 = model.S, model.d, model.Tmax + 1
-    log_init, log_jump, log_dwell, log_surv = f64(log_init), f64(log_jump), f64(log_dwell), f64(log_surv)
-    L = log_dwell.shape[1]
-    assert log_init.shape == (S,) and log_jump.shape == (S, S) and log_dwell.shape == (S, L) and log_surv.shape == (S, L)
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
     n = ts.n_traj
-    arrs = [f64(t) for t in trajs]
-    assert len(arrs) == n and all(len(a) == T for a, T in zip(arrs, ts.T))
-    x = f64(np.concatenate(arrs, axis=0))
-    keep = {}
-    for name, a, shape in (('dmsd', dmsd, (P, S, d, L1)), ('dmsd_inf', dmsd_inf, (P, S, d)), ('dmean', dmean, (P, S, d))):
-        if a is not None:
-            a = f64(a)
-            assert a.shape == shape, f"{name} has shape {a.shape}, expected {shape}"
-            keep[name] = a
-    derivs = GaussDerivs(**{k: aptr(a) if a.size else None for k, a in keep.items()})
+    T, x = _traj_block(trajs)
+    assert np.array_equal(T, ts.T)
+    derivs, keep = _gauss_derivs(model, P, dmsd, dmsd_inf, dmean)
     res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'grad': np.empty((n, P)), 'exp_logl': np.empty(n),
            'fisher': np.empty((n, P, P)) if fisher else None}
     spec = DwellsensOut(**{name: (aptr(a) if a is not None and a.size else None) for name, a in res.items()})
@@ -1439,9 +1431,7 @@ def gauss_dwell_lengths(model, ts, log_init, log_jump, log_dwell, log_surv, omit
     (n_traj, S, T_max), length l at column l - 1, 0 behind a trajectory's T; T_max the set's longest trajectory
     """
     S = model.S
-    log_init, log_jump, log_dwell, log_surv = f64(log_init), f64(log_jump), f64(log_dwell), f64(log_surv)
-    L = log_dwell.shape[1]
-    assert log_init.shape == (S,) and log_jump.shape == (S, S) and log_dwell.shape == (S, L) and log_surv.shape == (S, L)
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
     n = ts.n_traj
     T_max = int(np.max(ts.T))
     res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'exp_jumps': np.empty((n, S, S)),
@@ -1465,9 +1455,7 @@ def gauss_dwell_draw(model, ts, log_init, log_jump, log_dwell, log_surv, draw_tr
     consumed, U = ``keep_uniforms`` in device mode (None where U = 0); T_max the set's longest trajectory
     """
     S = model.S
-    log_init, log_jump, log_dwell, log_surv = f64(log_init), f64(log_jump), f64(log_dwell), f64(log_surv)
-    L = log_dwell.shape[1]
-    assert log_init.shape == (S,) and log_jump.shape == (S, S) and log_dwell.shape == (S, L) and log_surv.shape == (S, L)
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
     draw_traj = i32(draw_traj)
     n, U = len(draw_traj), int(keep_uniforms)
     assert draw_traj.shape == (n,)

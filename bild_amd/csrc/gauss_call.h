@@ -1,6 +1,8 @@
-// The frame of one exact-inference call (exact.cpp, gauss_segdp.cpp, gauss_segdraw.cpp, gauss_segsens.cpp, gauss_dwell.cpp,
-// gauss_dwelldraw.cpp, gauss_dwellsens.cpp; gauss_segtangent.cpp allocates through it): the lock that serialises the calls on
-// a stream, the stream, the device memory of the call and the rule that cuts the call into chunks.  Host only; private to the
+// The frame of one exact-inference call: the lock that serialises the calls on a stream, the stream, the device memory of the
+// call and the rule that cuts the call into chunks.  exact.cpp opens one itself; the calls on the segment recursion and on
+// the dwell-time recursion declare one and have it opened by the recursion's owner (SegdpCall of gauss_segdp.h: gauss_segdp.cpp,
+// gauss_segdraw.cpp, gauss_segsens.cpp; DwellCall of gauss_dwell.h: gauss_dwell.cpp, gauss_dwelldraw.cpp, gauss_dwellsens.cpp,
+// gauss_dwelllen.cpp); gauss_segtangent.cpp and DrawGroups (gauss_draws.h) allocate through it.  Host only; private to the
 // library.
 #pragma once
 #include "internal.h"
@@ -12,7 +14,7 @@ namespace bild {
 // stream, allocations, and the destructor undoes them from the other end: it first waits for the stream, so that no kernel
 // or copy still uses the memory, then frees the allocations, and only then (the lock is the first member) lets the next call
 // onto the stream.  That holds on every return path, an error path included.  Host vectors that asynchronous copies read
-// are declared before the frame, so that they outlive the wait.
+// or write are declared before the frame, so that they outlive the wait.
 struct CallFrame {
     std::unique_lock<std::mutex> lock;
     hipStream_t st = nullptr;

@@ -1,10 +1,11 @@
-// The bookkeeping of a call that draws profiles (gauss_segdraw.cpp, gauss_dwelldraw.cpp): what it refuses about the draws, and
-// the draws grouped by the trajectory they name, so that a chunk of trajectories finds its draws in one run.  Host only;
-// private to the library.
+// The bookkeeping of a call that draws profiles (gauss_segdraw.cpp, gauss_dwelldraw.cpp): what it refuses about the draws,
+// the draws grouped by the trajectory they name, so that a chunk of trajectories finds its draws in one run, and the device
+// descriptors of the trajectories that a draw names.  Host only; private to the library.
 #pragma once
 #include <limits>
 
-#include "likelihood.h"
+#include "gauss.h"
+#include "gauss_call.h"
 
 namespace bild {
 
@@ -20,6 +21,10 @@ struct DrawGroups {
     std::vector<int> first;         // the draws of used[u]: order[first[u]] .. order[first[u + 1] - 1]
     std::vector<int32_t> order;     // the draws grouped by trajectory; within a trajectory in the call's order
     std::vector<int32_t> slot_of;   // per place in `order`: the trajectory's place in its chunk (chunk())
+    std::vector<GaussTraj> mine;    // the descriptors of `used` (upload(); an asynchronous copy reads them)
+    const GaussTraj *d_used = nullptr;              // upload(): `mine` on the device; chunks run over it, not over the set
+    const int32_t *d_order = nullptr;               // ... and `order`
+    int32_t *d_slot = nullptr;                      // ... and room for `slot_of` (chunk())
     int Tm = 1;                     // the longest trajectory in `used`
 
     // Refuses, draw by draw, a draw_traj outside the set and (draw_k not NULL) a draw_k outside 0 .. k_max, then a replayed
@@ -55,13 +60,36 @@ struct DrawGroups {
         return BILD_OK;
     }
 
-    // the chunk of the nc trajectories used[u0 ..]: fills slot_of for its draws, which are places *i0 .. *i0 + *ni - 1 of `order`
-    void chunk(int u0, int nc, int *i0, int *ni)
+    // The set's descriptors back from the device, those of `used` gathered; they and `order` go up on the frame's stream,
+    // to memory of the frame.  The groups are declared BEFORE the frame.  A BILD_* code.
+    int upload(CallFrame &call, int n_traj)
+    {
+        std::vector<GaussTraj> all(n_traj);
+        GaussTraj *d = nullptr;
+        int32_t *d_o = nullptr;
+        BILD_TRY(call.alloc(&d, used.size()));
+        BILD_TRY(call.alloc(&d_o, order.size()));
+        BILD_TRY(call.alloc(&d_slot, order.size()));
+        HIP_TRY(hipMemcpy(all.data(), call.d_trajs, (size_t)n_traj * sizeof(GaussTraj), hipMemcpyDeviceToHost));
+        mine.resize(used.size());
+        for (size_t u = 0; u < used.size(); ++u) mine[u] = all[used[u]];
+        HIP_TRY(hipMemcpyAsync(d, mine.data(), mine.size() * sizeof(GaussTraj), hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(d_o, order.data(), order.size() * 4, hipMemcpyHostToDevice, call.st));
+        d_used = d;
+        d_order = d_o;
+        return BILD_OK;
+    }
+
+    // the chunk of the nc trajectories used[u0 ..]: fills slot_of for its draws, which are places *i0 .. *i0 + *ni - 1 of
+    // `order`, and sends that part of it to d_slot.  A BILD_* code.
+    int chunk(CallFrame &call, int u0, int nc, int *i0, int *ni)
     {
         for (int u = u0; u < u0 + nc; ++u)
             for (int i = first[u]; i < first[u + 1]; ++i) slot_of[i] = u - u0;
         *i0 = first[u0];
         *ni = first[u0 + nc] - *i0;
+        HIP_TRY(hipMemcpyAsync(d_slot + *i0, slot_of.data() + *i0, (size_t)*ni * 4, hipMemcpyHostToDevice, call.st));
+        return BILD_OK;
     }
 };
 

@@ -1,6 +1,9 @@
 // Exact inference under a dwell-time prior (include/bild_amd.h, "exact inference under a dwell-time prior"; DESIGN.md
-// section 21): the refusals and the upload of the prior (gauss_dwelldraw.cpp's as well), the chunks of whole trajectories,
-// the launches on the set's stream, and the NaN rule on what comes back.  Kernels: gauss_dwell.hip.
+// section 21).  DwellCall is the host side of the recursion that bild_gauss_dwell_evidence here, gauss_dwellsens.cpp,
+// gauss_dwelllen.cpp and gauss_dwelldraw.cpp share (gauss_dwell.h): the refusals, the frame on the set's stream, the chunks
+// of whole trajectories, the prior's upload, the tables, the kernels' parameters, the two passes, and the NaN rule on what
+// comes back.  Kernels: gauss_dwell.hip.
+#include <algorithm>
 #include <cmath>
 #include <limits>
 
@@ -21,10 +24,9 @@ int check_logs(const char *name, const double *a, size_t n)
     return BILD_OK;
 }
 
-} // namespace
-
-namespace bild {
-
+// What every call on a dwell-time prior refuses about the prior and the set's lengths: more than kDwellMaxS states, L < 1 or
+// shorter than a trajectory, a NaN or +inf table entry, a finite diagonal of log_jump, log_init that is -inf everywhere, a
+// negative scratch_bytes, T_max shorter than a trajectory.  A BILD_* code.
 int dwell_check_call(int S, int L, const double *log_init, const double *log_jump, const double *log_dwell, const double *log_surv,
                      int n_traj, const int *T, int T_max, int64_t scratch_bytes)
 {
@@ -50,19 +52,84 @@ int dwell_check_call(int S, int L, const double *log_init, const double *log_jum
     return BILD_OK;
 }
 
-int dwell_upload_prior(CallFrame &call, int S, int L, const double *log_init, const double *log_jump, const double *log_dwell,
-                       const double *log_surv, DwellPrior *prior)
+} // namespace
+
+namespace bild {
+
+DwellVerdict dwell_nan_rule(const double *fin, long long n_nan, bool omit)
 {
-    const size_t n_jump = (size_t)S * S, n_len = (size_t)S * L;
-    std::vector<double> host(S + n_jump + 2 * n_len);
-    std::copy_n(log_init, S, host.data());
-    std::copy_n(log_jump, n_jump, host.data() + S);
-    std::copy_n(log_dwell, n_len, host.data() + S + n_jump);
-    std::copy_n(log_surv, n_len, host.data() + S + n_jump + n_len);
+    const bool bad = !omit && n_nan > 0;
+    return DwellVerdict{bad, !bad && !std::isinf(fin[0]), bad ? std::numeric_limits<double>::quiet_NaN() : fin[0]};
+}
+
+int DwellCall::check(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L_, const double *log_init, const double *log_jump,
+                     const double *log_dwell, const double *log_surv, int T_max, unsigned flags, int64_t scratch, const void *out)
+{
+    BILD_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
+    if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
+    if (flags & ~BILD_DWELL_NAN_OMIT) return fail(BILD_ERR_INVALID, "flags = %u: unknown bits", flags);
+    S = m->S;
+    L = L_;
+    BILD_TRY(dwell_check_call(S, L, log_init, log_jump, log_dwell, log_surv, n_traj, T, T_max, scratch));
+    for (int j = 0; j < n_traj; ++j) Tm = std::max(Tm, T[j]);
+    n = n_traj;
+    omit = (flags & BILD_DWELL_NAN_OMIT) != 0;
+    scratch_bytes = scratch;
+    prior[0] = log_init, prior[1] = log_jump, prior[2] = log_dwell, prior[3] = log_surv;
+    return BILD_OK;
+}
+
+int DwellCall::open(CallFrame &call, const bild_gauss_model *m, const bild_gauss_trajset *ts, unsigned sets_, int64_t own_bytes)
+{
+    sets = sets_;
+    BILD_TRY(call.open(m, ts));
+    BILD_TRY(call.chunk_of(dwell_table_bytes(sets, S, Tm) + own_bytes, scratch_bytes, n, &chunk));
+
+    // the four prior tables in one device block (synchronous copy: `host` ends here)
+    const size_t len[4] = {(size_t)S, (size_t)S * S, (size_t)S * L, (size_t)S * L};
+    const double **member[4] = {&p.log_init, &p.log_jump, &p.log_dwell, &p.log_surv};
+    std::vector<double> host;
+    for (int t = 0; t < 4; ++t) host.insert(host.end(), prior[t], prior[t] + len[t]);
     double *d = nullptr;
     BILD_TRY(call.alloc(&d, host.size()));
-    HIP_TRY(hipMemcpy(d, host.data(), host.size() * 8, hipMemcpyHostToDevice));     // (synchronous: `host` ends here)
-    *prior = DwellPrior{d, d + S, d + S + n_jump, d + S + n_jump + n_len};
+    HIP_TRY(hipMemcpy(d, host.data(), host.size() * 8, hipMemcpyHostToDevice));
+    for (int t = 0; t < 4; d += len[t++]) *member[t] = d;
+
+    const int ld = Tm + 1, ntile = dwell_ntile(Tm);
+    const int64_t slot = (int64_t)S * ld;
+#define X(name, set, entries) \
+    if (sets & (set)) BILD_TRY(call.alloc(&p.name, (size_t)chunk * (size_t)(entries)));
+    BILD_DWELL_TABLES(X)
+#undef X
+    p.slot = slot;
+    p.S = S;
+    p.L = L;
+    p.Tm = Tm;
+    p.ld = ld;
+    p.ntile = ntile;
+    if (sets & kDwellForward) {
+        fin.resize((size_t)chunk * 2);
+        n_nan.resize((size_t)chunk);
+    }
+    return BILD_OK;
+}
+
+int DwellCall::run(CallFrame &call, const GaussTraj *trajs, int nc)
+{
+    p.trajs = trajs;
+    p.n_traj = nc;
+    if ((sets & kDwellForward) && launch_dwell_forward(p, call.st))
+        return fail(BILD_ERR_HIP, "launch of the forward pass of the dwell-time recursion failed");
+    if ((sets & kDwellBackward) && launch_dwell_backward(p, call.st))
+        return fail(BILD_ERR_HIP, "launch of the backward pass of the dwell-time recursion failed");
+    return BILD_OK;
+}
+
+int DwellCall::read_back(CallFrame &call, int nc)
+{
+    HIP_TRY(hipMemcpyAsync(fin.data(), p.fin, (size_t)nc * 2 * 8, hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(n_nan.data(), p.n_nan, (size_t)nc * sizeof(long long), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipStreamSynchronize(call.st));
     return BILD_OK;
 }
 
@@ -72,108 +139,62 @@ extern "C" int bild_gauss_dwell_evidence(const bild_gauss_model *m, const bild_g
                                          const double *log_jump, const double *log_dwell, const double *log_surv, int T_max,
                                          unsigned flags, int64_t scratch_bytes, bild_dwell_out *out)
 {
-    int n_traj = 0;
-    const int *T = nullptr;
-    BILD_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
-    if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
-    if (flags & ~BILD_DWELL_NAN_OMIT) return fail(BILD_ERR_INVALID, "flags = %u: unknown bits", flags);
-    const int S = m->S;
-    BILD_TRY(dwell_check_call(S, L, log_init, log_jump, log_dwell, log_surv, n_traj, T, T_max, scratch_bytes));
-    int Tm = 1;
-    for (int j = 0; j < n_traj; ++j) Tm = std::max(Tm, T[j]);
-    if (n_traj == 0) return BILD_OK;
-    const bool omit = (flags & BILD_DWELL_NAN_OMIT) != 0, marg = out->log_post != nullptr;
-    const bool stats = marg;    // log_post == NULL: the forward pass alone
-    const int ld = Tm + 1, ntile = (Tm + kDwellTile - 1) / kDwellTile;
-    const int64_t slot = (int64_t)S * ld, rows = (int64_t)S * ntile * Tm;
+    DwellCall rec;      // (before the frame, with the host copies below: asynchronous copies write them)
+    std::vector<double> post, jumps, stay;
+    std::vector<uint8_t> states;
+    BILD_TRY(rec.check(m, ts, L, log_init, log_jump, log_dwell, log_surv, T_max, flags, scratch_bytes, out));
+    if (rec.n_traj == 0) return BILD_OK;
+    const bool stats = out->log_post != nullptr;    // log_post == NULL: the forward pass alone
+    const int S = rec.S, Tm = rec.Tm;
 
     CallFrame call;
-    BILD_TRY(call.open(m, ts));
+    BILD_TRY(rec.open(call, m, ts, stats ? kDwellForward | kDwellBackward | kDwellStats : kDwellForward, 0));
     hipStream_t st = call.st;
+    const DwellParams &p = rec.p;
+    const int chunk = rec.chunk, ld = p.ld;
+    const int64_t slot = p.slot;
 
-    const int64_t per_traj = slot * (4 * 8 + 2 * 4 + (stats ? 4 * 8 : 0)) + (stats ? (rows + (int64_t)S * ntile + S * S + S) * 8 : 0) + Tm + 24;
-    int chunk = 0;
-    BILD_TRY(call.chunk_of(per_traj, scratch_bytes, n_traj, &chunk));
-
-    DwellParams p{};
-    DwellPrior dp{};
-    BILD_TRY(dwell_upload_prior(call, S, L, log_init, log_jump, log_dwell, log_surv, &dp));
-    BILD_TRY(call.alloc(&p.A, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.AV, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.alpha, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.alphaV, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.Aarg, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.alphaArg, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.fin, (size_t)chunk * 2));
-    BILD_TRY(call.alloc(&p.n_nan, (size_t)chunk));
-    BILD_TRY(call.alloc(&p.map_states, (size_t)chunk * Tm));
     if (stats) {
-        BILD_TRY(call.alloc(&p.beta, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.gamma, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.cover, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.post, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.row_tot, (size_t)chunk * rows));
-        BILD_TRY(call.alloc(&p.stay_part, (size_t)chunk * S * ntile));
-        BILD_TRY(call.alloc(&p.jumps, (size_t)chunk * S * S));
-        BILD_TRY(call.alloc(&p.stay, (size_t)chunk * S));
+        post.resize((size_t)chunk * slot);
+        jumps.resize((size_t)chunk * S * S);
+        stay.resize((size_t)chunk * S);
     }
-    p.log_init = dp.log_init;
-    p.log_jump = dp.log_jump;
-    p.log_dwell = dp.log_dwell;
-    p.log_surv = dp.log_surv;
-    p.slot = slot;
-    p.S = S;
-    p.L = L;
-    p.Tm = Tm;
-    p.ld = ld;
-    p.ntile = ntile;
-
-    std::vector<double> fin((size_t)chunk * 2), post(stats ? (size_t)chunk * slot : 0), jumps(stats ? (size_t)chunk * S * S : 0),
-        stay(stats ? (size_t)chunk * S : 0);
-    std::vector<long long> n_nan((size_t)chunk);
-    std::vector<uint8_t> states((size_t)chunk * Tm);
+    states.resize((size_t)chunk * Tm);
     const double nan = std::numeric_limits<double>::quiet_NaN();
 
-    for (int j0 = 0; j0 < n_traj; j0 += chunk) {
-        const int nc = std::min(chunk, n_traj - j0);
-        p.trajs = call.d_trajs + j0;
-        p.n_traj = nc;
-        if (launch_dwell_forward(p, st)) return fail(BILD_ERR_HIP, "launch of the forward pass of the dwell-time recursion failed");
+    for (int j0 = 0; j0 < rec.n_traj; j0 += chunk) {
+        const int nc = std::min(chunk, rec.n_traj - j0);
+        BILD_TRY(rec.run(call, call.d_trajs + j0, nc));
         if (stats) {
-            if (launch_dwell_backward(p, st)) return fail(BILD_ERR_HIP, "launch of the backward pass of the dwell-time recursion failed");
             if (launch_dwell_cover(p, st) || launch_dwell_carry(p, st) || launch_dwell_counts(p, st))
                 return fail(BILD_ERR_HIP, "launch of the statistics of the dwell-time recursion failed");
             HIP_TRY(hipMemcpyAsync(post.data(), p.post, (size_t)nc * slot * 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(jumps.data(), p.jumps, (size_t)nc * S * S * 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(stay.data(), p.stay, (size_t)nc * S * 8, hipMemcpyDeviceToHost, st));
         }
-        HIP_TRY(hipMemcpyAsync(fin.data(), p.fin, (size_t)nc * 2 * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(n_nan.data(), p.n_nan, (size_t)nc * sizeof(long long), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(states.data(), p.map_states, (size_t)nc * Tm, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        BILD_TRY(rec.read_back(call, nc));
 
         for (int i = 0; i < nc; ++i) {
-            const int jt = j0 + i, Tj = T[jt];
-            const bool bad = !omit && n_nan[i] > 0;
-            const double logev = bad ? nan : fin[2 * i];
-            const bool usable = !bad && !std::isinf(fin[2 * i]);
-            if (out->logev) out->logev[jt] = logev;
-            if (out->map_logjoint) out->map_logjoint[jt] = fin[2 * i + 1];
-            if (out->n_nan_windows) out->n_nan_windows[jt] = n_nan[i];
+            const int jt = j0 + i, Tj = rec.T[jt];
+            const DwellVerdict v = rec.verdict(i);
+            if (out->logev) out->logev[jt] = v.logev;
+            if (out->map_logjoint) out->map_logjoint[jt] = rec.fin[2 * i + 1];
+            if (out->n_nan_windows) out->n_nan_windows[jt] = rec.n_nan[i];
             if (out->map_states) {
                 uint8_t *row = out->map_states + (size_t)jt * T_max;
                 for (int t = 0; t < T_max; ++t) row[t] = t < Tj ? states[(size_t)i * Tm + t] : 255;
             }
-            if (marg) {
+            if (stats) {
                 double *lp = out->log_post + (size_t)jt * S * T_max;
                 for (int s = 0; s < S; ++s)
                     for (int t = 0; t < T_max; ++t)
-                        lp[(size_t)s * T_max + t] = usable && t < Tj ? std::log(post[(size_t)i * slot + (size_t)s * ld + t]) : nan;
+                        lp[(size_t)s * T_max + t] = v.usable && t < Tj ? std::log(post[(size_t)i * slot + (size_t)s * ld + t]) : nan;
             }
             if (stats && out->exp_jumps)
-                for (int e = 0; e < S * S; ++e) out->exp_jumps[(size_t)jt * S * S + e] = usable ? jumps[(size_t)i * S * S + e] : nan;
+                for (int e = 0; e < S * S; ++e) out->exp_jumps[(size_t)jt * S * S + e] = v.usable ? jumps[(size_t)i * S * S + e] : nan;
             if (stats && out->exp_stay)
-                for (int s = 0; s < S; ++s) out->exp_stay[(size_t)jt * S + s] = usable ? stay[(size_t)i * S + s] : nan;
+                for (int s = 0; s < S; ++s) out->exp_stay[(size_t)jt * S + s] = v.usable ? stay[(size_t)i * S + s] : nan;
         }
     }
     return BILD_OK;

@@ -13,7 +13,11 @@
 #pragma once
 #include <stdint.h>
 
+#include <vector>
+
 #include "gauss.h"
+
+struct bild_gauss_trajset;
 
 namespace bild {
 
@@ -43,20 +47,91 @@ struct DwellParams {
     int n_traj, S, L, Tm, ld, ntile;
 };
 
-// What every call on a dwell-time prior refuses about the prior and the set's lengths (gauss_dwell.cpp; host only): more than
-// kDwellMaxS states, L < 1 or shorter than a trajectory, a NaN or +inf table entry, a finite diagonal of log_jump, log_init
-// that is -inf everywhere, a negative scratch_bytes, T_max shorter than a trajectory.  A BILD_* code.
-int dwell_check_call(int S, int L, const double *log_init, const double *log_jump, const double *log_dwell, const double *log_surv,
-                     int n_traj, const int *T, int T_max, int64_t scratch_bytes);
-
-// The four prior tables in one device block: packed, allocated through the frame and uploaded by a synchronous copy.  The
-// device pointers in *prior.  A BILD_* code.
+// ---- the host side that the calls on the recursion share (gauss_dwell.cpp; evidence, sensitivities, lengths, draws) ----
 struct CallFrame;
-struct DwellPrior {
-    const double *log_init, *log_jump, *log_dwell, *log_surv;
+
+// The per-trajectory tables of the recursion: the member of DwellParams (its element size is the table's), the set it
+// belongs to and its entries per trajectory (S states, Tm frames, slot = S * (Tm + 1), ntile tiles).  What a trajectory
+// costs (dwell_table_bytes) and what a call allocates (DwellCall::open) both come from this list and from nowhere else.
+enum : unsigned {
+    kDwellForward = 1u,     // what launch_dwell_forward writes
+    kDwellBackward = 2u,    // beta and gamma
+    kDwellJumps = 4u,       // launch_dwell_counts' jump half (stay_part null)
+    kDwellCover = 8u,       // launch_dwell_cover and _carry, and the stay half of the counts
+    kDwellStats = kDwellCover | kDwellJumps,
 };
-int dwell_upload_prior(CallFrame &call, int S, int L, const double *log_init, const double *log_jump, const double *log_dwell,
-                       const double *log_surv, DwellPrior *prior);
+#define BILD_DWELL_TABLES(X)                            \
+    X(A, kDwellForward, slot)                           \
+    X(AV, kDwellForward, slot)                          \
+    X(alpha, kDwellForward, slot)                       \
+    X(alphaV, kDwellForward, slot)                      \
+    X(Aarg, kDwellForward, slot)                        \
+    X(alphaArg, kDwellForward, slot)                    \
+    X(fin, kDwellForward, 2)                            \
+    X(n_nan, kDwellForward, 1)                          \
+    X(map_states, kDwellForward, Tm)                    \
+    X(beta, kDwellBackward, slot)                       \
+    X(gamma, kDwellBackward, slot)                      \
+    X(jumps, kDwellJumps, (int64_t)S * S)               \
+    X(cover, kDwellCover, slot)                         \
+    X(post, kDwellCover, slot)                          \
+    X(row_tot, kDwellCover, (int64_t)S * ntile * Tm)    \
+    X(stay_part, kDwellCover, (int64_t)S * ntile)       \
+    X(stay, kDwellCover, S)
+constexpr int dwell_ntile(int Tm) { return (Tm + kDwellTile - 1) / kDwellTile; }
+
+// bytes of one trajectory in the tables of `sets` (needs no device)
+inline int64_t dwell_table_bytes(unsigned sets, int S, int Tm)
+{
+    const DwellParams p{};
+    const int ntile = dwell_ntile(Tm);
+    const int64_t slot = (int64_t)S * (Tm + 1);
+    int64_t bytes = 0;
+#define X(name, set, entries) \
+    if (sets & (set)) bytes += (int64_t)(entries) * (int64_t)sizeof(*p.name);
+    BILD_DWELL_TABLES(X)
+#undef X
+    return bytes;
+}
+
+// Section 21's NaN rule on what the forward pass leaves of a trajectory (fin: its pair; n_nan: its skipped NaN windows; omit:
+// BILD_DWELL_NAN_OMIT): bad = the evidence is NaN, usable = it is a finite number, and every statistic with it.
+struct DwellVerdict {
+    bool bad, usable;
+    double logev;
+};
+DwellVerdict dwell_nan_rule(const double *fin, long long n_nan, bool omit);
+
+// One call on the recursion.  Declared BEFORE the call's CallFrame: asynchronous copies write its vectors, so they must
+// outlive the frame's wait.  In this order:
+//   check()      what a call refuses before it touches the device: out, flags, dwell_check_call.  Fills n_traj, T, S, L, omit
+//                and Tm (the set's longest, at least 1).  Where n_traj is 0, a call returns BILD_OK behind it.
+//   over()       (the draws) the chunks run over n of the set's trajectories, the longest of Tm frames
+//   open()       the frame on the set's stream, the chunks (a trajectory costs the tables of `sets` and the call's own
+//                `own_bytes`), the prior's upload, the tables and p
+//   run()        per chunk: the forward pass (kDwellForward) and the backward pass (kDwellBackward) of nc trajectories
+//   read_back()  fin and n_nan of the chunk, and the wait for the stream; verdict(i) is dwell_nan_rule on trajectory i
+struct DwellCall {
+    int n_traj = 0, n = 0, S = 0, L = 0, Tm = 1, chunk = 0;
+    const int *T = nullptr;
+    bool omit = false;
+    DwellParams p{};
+    std::vector<double> fin;
+    std::vector<long long> n_nan;
+
+    int check(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init, const double *log_jump,
+              const double *log_dwell, const double *log_surv, int T_max, unsigned flags, int64_t scratch_bytes, const void *out);
+    void over(int n_used, int Tm_used) { n = n_used, Tm = Tm_used; }
+    int open(CallFrame &call, const bild_gauss_model *m, const bild_gauss_trajset *ts, unsigned sets, int64_t own_bytes);
+    int run(CallFrame &call, const GaussTraj *trajs, int nc);
+    int read_back(CallFrame &call, int nc);
+    DwellVerdict verdict(int i) const { return dwell_nan_rule(fin.data() + 2 * i, n_nan[i], omit); }
+
+private:
+    const double *prior[4] = {};
+    int64_t scratch_bytes = 0;
+    unsigned sets = 0;
+};
 
 int launch_dwell_forward(const DwellParams &p, void *stream);
 int launch_dwell_backward(const DwellParams &p, void *stream);

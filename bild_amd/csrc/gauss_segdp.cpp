@@ -1,7 +1,9 @@
 // Exact evidence of every k by a segment recursion (include/bild_amd.h, "exact evidence of every k"):
-// the refusals, the chunks of whole trajectories, the launches level after level on the set's stream, and the host's
-// formulas on the last column of the forward table.  The refusals, the counts, the launch sequences and the formulas are
-// also what gauss_segdraw.cpp and gauss_segsens.cpp call (gauss_segdp.h).  Kernels: gauss_segdp.hip.
+// SegdpCall is the host side of the recursion that bild_gauss_segment_evidence here, gauss_segsens.cpp and
+// gauss_segdraw.cpp share (gauss_segdp.h): the refusals, the frame on the set's stream, the chunks of whole trajectories, the
+// transitions' upload, the tables, the kernels' parameters, the launches level after level, and the host's formulas on the
+// last column of the forward table, k by k.  Kernels: gauss_segdp.hip.
+#include <algorithm>
 #include <cmath>
 #include <limits>
 
@@ -18,8 +20,10 @@ int segdp_check_transitions(int S, const uint8_t *transitions)
     return BILD_OK;
 }
 
-int segdp_check_call(int S, int k_max, unsigned flags, const uint8_t *transitions, int64_t scratch_bytes, int n_traj, const int *T,
-                     int T_max)
+// What every call on the recursion refuses, in this order: k_max outside 0 .. kSegdpMaxK, flags other than BILD_SEGDP_NAN_OMIT,
+// the transitions, a negative scratch_bytes, T_max shorter than a trajectory.  A BILD_* code.
+static int segdp_check_call(int S, int k_max, unsigned flags, const uint8_t *transitions, int64_t scratch_bytes, int n_traj,
+                            const int *T, int T_max)
 {
     if (k_max < 0 || k_max > kSegdpMaxK)
         return fail(BILD_ERR_UNSUPPORTED, "k_max = %d: the segment recursion supports 0 <= k_max <= %d", k_max, kSegdpMaxK);
@@ -63,16 +67,6 @@ std::vector<long double> trace_counts(int S, const uint8_t *tr, int K)
         v.swap(w);
     }
     return out;
-}
-
-int alloc_fwd(CallFrame &call, SegdpFwd *t, size_t n)
-{
-    BILD_TRY(call.alloc(&t->M, n));
-    BILD_TRY(call.alloc(&t->Z, n));
-    BILD_TRY(call.alloc(&t->R, n));
-    BILD_TRY(call.alloc(&t->ok, n));
-    BILD_TRY(call.alloc(&t->bad, n));
-    return call.alloc(&t->arg, n);
 }
 
 SegdpEvidence segdp_evidence(const double *f, int S, long double n_all, bool omit)
@@ -129,50 +123,38 @@ int segdp_run_backward(const SegdpParams &p, int k_max, void *st)
     return BILD_OK;
 }
 
-} // namespace bild
-
-extern "C" int bild_gauss_segment_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k_max, const uint8_t *transitions,
-                                           int T_max, unsigned flags, int64_t scratch_bytes, bild_segdp_out *out)
+int SegdpCall::check(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k_max_, const uint8_t *tr, int T_max, unsigned flags,
+                     int64_t scratch, const void *out)
 {
-    int n_traj = 0;
-    const int *T = nullptr;
     BILD_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
     if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
-    const int S = m->S;
-    BILD_TRY(segdp_check_call(S, k_max, flags, transitions, scratch_bytes, n_traj, T, T_max));
-    int Tm = 1;
+    S = m->S;
+    BILD_TRY(segdp_check_call(S, k_max_, flags, tr, scratch, n_traj, T, T_max));
     for (int j = 0; j < n_traj; ++j) Tm = std::max(Tm, T[j]);
-    if (n_traj == 0) return BILD_OK;
-    const bool omit = (flags & BILD_SEGDP_NAN_OMIT) != 0, marg = out->log_post != nullptr;
-    const int K = k_max + 1, ld = Tm + 1, ntile = (Tm + kSegdpTile - 1) / kSegdpTile;
-    const int64_t slot = (int64_t)K * S * ld, rows = (int64_t)K * S * ntile * Tm;
+    n = n_traj;
+    k_max = k_max_;
+    K = k_max + 1;
+    omit = (flags & BILD_SEGDP_NAN_OMIT) != 0;
+    transitions = tr;
+    scratch_bytes = scratch;
+    return BILD_OK;
+}
 
-    CallFrame call;
+int SegdpCall::open(CallFrame &call, const bild_gauss_model *m, const bild_gauss_trajset *ts, unsigned sets_, int64_t own_bytes)
+{
+    sets = sets_;
     BILD_TRY(call.open(m, ts));
-    hipStream_t st = call.st;
+    BILD_TRY(call.chunk_of(segdp_table_bytes(sets, S, K, Tm) + own_bytes, scratch_bytes, n, &chunk));
 
-    const int64_t per_traj = slot * (2 * (5 * 8 + 4) + (marg ? 6 * 8 : 0)) + (marg ? rows * 8 : 0) + (int64_t)K * K * 8 + (int64_t)K * S * 40;
-    int chunk = 0;
-    BILD_TRY(call.chunk_of(per_traj, scratch_bytes, n_traj, &chunk));
-
-    SegdpParams p{};
     uint8_t *d_tr = nullptr;
     BILD_TRY(call.alloc(&d_tr, (size_t)S * S));
-    BILD_TRY(alloc_fwd(call, &p.A, (size_t)chunk * slot));
-    BILD_TRY(alloc_fwd(call, &p.alpha, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.map_seg_start, (size_t)chunk * K * K));
-    BILD_TRY(call.alloc(&p.map_seg_state, (size_t)chunk * K * K));
-    BILD_TRY(call.alloc(&p.fin, (size_t)chunk * K * S * 5));
-    if (marg) {
-        BILD_TRY(call.alloc(&p.beta.M, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.beta.Z, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.gamma.M, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.gamma.Z, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.cover, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.post, (size_t)chunk * slot));
-        BILD_TRY(call.alloc(&p.row_tot, (size_t)chunk * rows));
-    }
-    HIP_TRY(hipMemcpy(d_tr, transitions, (size_t)S * S, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_tr, transitions, (size_t)S * S, hipMemcpyHostToDevice));    // (synchronous: caller memory)
+    const int ld = Tm + 1, ntile = segdp_ntile(Tm);
+    const int64_t slot = (int64_t)K * S * ld;
+#define X(member, set, entries) \
+    if (sets & (set)) BILD_TRY(call.alloc(&p.member, (size_t)chunk * (size_t)(entries)));
+    BILD_SEGDP_TABLES(X)
+#undef X
     p.tr = d_tr;
     p.slot = slot;
     p.S = S;
@@ -180,41 +162,77 @@ extern "C" int bild_gauss_segment_evidence(const bild_gauss_model *m, const bild
     p.Tm = Tm;
     p.ld = ld;
     p.ntile = ntile;
+    if (sets & kSegdpForward) {
+        fin.resize((size_t)chunk * K * S * 5);
+        ntraces = trace_counts(S, transitions, K);
+    }
+    return BILD_OK;
+}
 
-    const std::vector<long double> ntraces = trace_counts(S, transitions, K);
-    std::vector<double> fin((size_t)chunk * K * S * 5), post(marg ? (size_t)chunk * slot : 0);
-    std::vector<int32_t> seg_a((size_t)chunk * K * K), seg_v((size_t)chunk * K * K);
+int SegdpCall::run(CallFrame &call, const GaussTraj *trajs, int nc)
+{
+    p.trajs = trajs;
+    p.n_traj = nc;
+    if (sets & kSegdpForward) BILD_TRY(segdp_run_forward(p, k_max, call.st));
+    if (sets & kSegdpBackward) BILD_TRY(segdp_run_backward(p, k_max, call.st));
+    return BILD_OK;
+}
+
+int SegdpCall::read_back(CallFrame &call, int nc)
+{
+    HIP_TRY(hipMemcpyAsync(fin.data(), p.fin, (size_t)nc * K * S * 5 * 8, hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipStreamSynchronize(call.st));
+    return BILD_OK;
+}
+
+} // namespace bild
+
+extern "C" int bild_gauss_segment_evidence(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k_max, const uint8_t *transitions,
+                                           int T_max, unsigned flags, int64_t scratch_bytes, bild_segdp_out *out)
+{
+    SegdpCall rec;      // (before the frame, with the host copies below: asynchronous copies write them)
+    std::vector<double> post;
+    std::vector<int32_t> seg_a, seg_v;
+    BILD_TRY(rec.check(m, ts, k_max, transitions, T_max, flags, scratch_bytes, out));
+    if (rec.n_traj == 0) return BILD_OK;
+    const bool marg = out->log_post != nullptr;
+    const int S = rec.S, K = rec.K;
+
+    CallFrame call;
+    BILD_TRY(rec.open(call, m, ts, marg ? kSegdpForward | kSegdpBackward | kSegdpCover : kSegdpForward, 0));
+    hipStream_t st = call.st;
+    const SegdpParams &p = rec.p;
+    const int chunk = rec.chunk, ld = p.ld;
+    const int64_t slot = p.slot;
+
+    post.resize(marg ? (size_t)chunk * slot : 0);
+    seg_a.resize((size_t)chunk * K * K);
+    seg_v.resize((size_t)chunk * K * K);
     const double nan = std::numeric_limits<double>::quiet_NaN();
 
-    for (int j0 = 0; j0 < n_traj; j0 += chunk) {
-        const int nc = std::min(chunk, n_traj - j0);
-        p.trajs = call.d_trajs + j0;
-        p.n_traj = nc;
-        BILD_TRY(segdp_run_forward(p, k_max, st));
+    for (int j0 = 0; j0 < rec.n_traj; j0 += chunk) {
+        const int nc = std::min(chunk, rec.n_traj - j0);
+        BILD_TRY(rec.run(call, call.d_trajs + j0, nc));
         if (marg) {
-            BILD_TRY(segdp_run_backward(p, k_max, st));
             if (launch_segdp_cover(p, st) || launch_segdp_carry(p, st)) return fail(BILD_ERR_HIP, "launch of the marginal kernels failed");
             HIP_TRY(hipMemcpyAsync(post.data(), p.post, (size_t)nc * slot * 8, hipMemcpyDeviceToHost, st));
         }
-        HIP_TRY(hipMemcpyAsync(fin.data(), p.fin, (size_t)nc * K * S * 5 * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(seg_a.data(), p.map_seg_start, (size_t)nc * K * K * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(seg_v.data(), p.map_seg_state, (size_t)nc * K * K * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        BILD_TRY(rec.read_back(call, nc));
 
         for (int i = 0; i < nc; ++i) {
-            const int jt = j0 + i, Tj = T[jt];
-            for (int k = 0; k < K; ++k) {
+            const int jt = j0 + i, Tj = rec.T[jt];
+            rec.each_k(i, Tj, [&](int k, const SegdpEvidence &e) {
                 const size_t o = (size_t)jt * K + k;
-                const SegdpEvidence e =
-                    segdp_evidence(fin.data() + ((size_t)i * K + k) * S * 5, S, binom_ld(Tj - 1, k) * ntraces[k], omit);
                 if (out->logev) out->logev[o] = e.logev;
                 if (out->kl) out->kl[o] = e.kl;
                 if (out->map_logl) out->map_logl[o] = e.map_logl;
                 if (out->n_profiles) out->n_profiles[o] = e.count;
-                if (out->n_omitted) out->n_omitted[o] = e.any && omit ? e.bad : 0.0;
+                if (out->n_omitted) out->n_omitted[o] = e.any && rec.omit ? e.bad : 0.0;
                 if (out->map_seg_start) std::copy_n(seg_a.data() + ((size_t)i * K + k) * K, K, out->map_seg_start + o * K);
                 if (out->map_seg_state) std::copy_n(seg_v.data() + ((size_t)i * K + k) * K, K, out->map_seg_state + o * K);
-                if (!marg) continue;
+                if (!marg) return;
                 double *lp = out->log_post + o * S * T_max;
                 const double *ps = post.data() + (size_t)i * slot + (size_t)k * S * ld;
                 for (int t = 0; t < T_max; ++t) {
@@ -224,7 +242,7 @@ extern "C" int bild_gauss_segment_evidence(const bild_gauss_model *m, const bild
                         for (int s = 0; s < S; ++s) tot += ps[(size_t)s * ld + t];
                     for (int s = 0; s < S; ++s) lp[(size_t)s * T_max + t] = in ? std::log(ps[(size_t)s * ld + t]) - std::log(tot) : nan;
                 }
-            }
+            });
         }
     }
     return BILD_OK;

@@ -21,6 +21,8 @@
 
 #include "gauss.h"
 
+struct bild_gauss_trajset;
+
 namespace bild {
 
 constexpr int kSegdpMaxK = 64;      // k_max of one call
@@ -67,16 +69,50 @@ struct CallFrame;
 
 // transitions: not NULL, entries 0 or 1 (exact.cpp as well).  A BILD_* code.
 int segdp_check_transitions(int S, const uint8_t *transitions);
-// What every call on the recursion refuses, in this order: k_max outside 0 .. kSegdpMaxK, flags other than BILD_SEGDP_NAN_OMIT,
-// the transitions, a negative scratch_bytes, T_max shorter than a trajectory.  A BILD_* code.
-int segdp_check_call(int S, int k_max, unsigned flags, const uint8_t *transitions, int64_t scratch_bytes, int n_traj, const int *T,
-                     int T_max);
 
 // C(n, k) from exact integer steps (each division is exact), carried in a 64-bit mantissa once it no longer fits 128 bits
 long double binom_ld(int n, int k);
 // valid traces of k switches for every k < K: the sum of the entries of transitions^k
 std::vector<long double> trace_counts(int S, const uint8_t *tr, int K);
-int alloc_fwd(CallFrame &call, SegdpFwd *t, size_t n);
+
+// The per-trajectory tables of the recursion: the member of SegdpParams (its element size is the table's), the set it
+// belongs to and its entries per trajectory (S states, K levels, Tm frames, slot = K * S * (Tm + 1), ntile tiles).  What a
+// trajectory costs (segdp_table_bytes) and what a call allocates (SegdpCall::open) both come from this list and from nowhere else.
+enum : unsigned {
+    kSegdpForward = 1u,     // A and alpha, the MAP arrays and fin: what segdp_run_forward writes
+    kSegdpBackward = 2u,    // beta and gamma
+    kSegdpCover = 4u,       // launch_segdp_cover and _carry
+};
+#define BILD_SEGDP_FWD(X, t) /* a SegdpFwd */                                                                   \
+    X(t.M, kSegdpForward, slot) X(t.Z, kSegdpForward, slot) X(t.R, kSegdpForward, slot) X(t.ok, kSegdpForward, slot) \
+    X(t.bad, kSegdpForward, slot) X(t.arg, kSegdpForward, slot)
+#define BILD_SEGDP_TABLES(X)                                                                \
+    BILD_SEGDP_FWD(X, A)                                                                    \
+    BILD_SEGDP_FWD(X, alpha)                                                                \
+    X(map_seg_start, kSegdpForward, (int64_t)K * K)                                         \
+    X(map_seg_state, kSegdpForward, (int64_t)K * K)                                         \
+    X(fin, kSegdpForward, (int64_t)K * S * 5)                                               \
+    X(beta.M, kSegdpBackward, slot) X(beta.Z, kSegdpBackward, slot)                         \
+    X(gamma.M, kSegdpBackward, slot) X(gamma.Z, kSegdpBackward, slot)                       \
+    X(cover, kSegdpCover, slot)                                                             \
+    X(post, kSegdpCover, slot)                                                              \
+    X(row_tot, kSegdpCover, (int64_t)K * S * ntile * Tm)
+
+constexpr int segdp_ntile(int Tm) { return (Tm + kSegdpTile - 1) / kSegdpTile; }
+
+// bytes of one trajectory in the tables of `sets` (needs no device)
+inline int64_t segdp_table_bytes(unsigned sets, int S, int K, int Tm)
+{
+    const SegdpParams p{};
+    const int ntile = segdp_ntile(Tm);
+    const int64_t slot = (int64_t)K * S * (Tm + 1);
+    int64_t bytes = 0;
+#define X(member, set, entries) \
+    if (sets & (set)) bytes += (int64_t)(entries) * (int64_t)sizeof(*p.member);
+    BILD_SEGDP_TABLES(X)
+#undef X
+    return bytes;
+}
 
 // The profiles of one (trajectory, k) from the S x 5 block `fin` of the last column of the forward table; n_all = all
 // profiles of that k, omit = BILD_SEGDP_NAN_OMIT.  logev = top + log(z) - log(count); z = 0 where logev is -inf or NaN.
@@ -89,5 +125,40 @@ SegdpEvidence segdp_evidence(const double *fin, int S, long double n_all, bool o
 // the launches of one chunk: init, then mix and level per j, then the back-pointer walk / init, then blevel and bmix per level
 int segdp_run_forward(const SegdpParams &p, int k_max, void *stream);
 int segdp_run_backward(const SegdpParams &p, int k_max, void *stream);
+
+// One call on the recursion, shaped as DwellCall (gauss_dwell.h) and, like it, declared BEFORE the call's CallFrame.
+//   check()      what a call refuses before it touches the device: out, segdp_check_call.  Fills n_traj, T, S, K, k_max, omit
+//                and Tm (the set's longest, at least 1).  Where n_traj is 0, a call returns BILD_OK behind it.
+//   over()       (the draws) the chunks run over n of the set's trajectories, the longest of Tm frames
+//   open()       the frame on the set's stream, the chunks (a trajectory costs the tables of `sets` and the call's own
+//                `own_bytes`), the transitions' upload, the tables, p and the trace counts
+//   run()        per chunk: segdp_run_forward (kSegdpForward) and segdp_run_backward (kSegdpBackward) of nc trajectories
+//   read_back()  fin of the chunk, and the wait for the stream
+//   each_k()     f(k, the SegdpEvidence of k) for every k of trajectory i of the chunk, which has Tj frames
+struct SegdpCall {
+    int n_traj = 0, n = 0, S = 0, K = 0, k_max = 0, Tm = 1, chunk = 0;
+    const int *T = nullptr;
+    bool omit = false;
+    SegdpParams p{};
+    std::vector<double> fin;
+    std::vector<long double> ntraces;
+
+    int check(const bild_gauss_model *m, const bild_gauss_trajset *ts, int k_max, const uint8_t *transitions, int T_max, unsigned flags,
+              int64_t scratch_bytes, const void *out);
+    void over(int n_used, int Tm_used) { n = n_used, Tm = Tm_used; }
+    int open(CallFrame &call, const bild_gauss_model *m, const bild_gauss_trajset *ts, unsigned sets, int64_t own_bytes);
+    int run(CallFrame &call, const GaussTraj *trajs, int nc);
+    int read_back(CallFrame &call, int nc);
+    template <class F> void each_k(int i, int Tj, F f) const
+    {
+        for (int k = 0; k < K; ++k)
+            f(k, segdp_evidence(fin.data() + ((size_t)i * K + k) * S * 5, S, binom_ld(Tj - 1, k) * ntraces[k], omit));
+    }
+
+private:
+    const uint8_t *transitions = nullptr;
+    int64_t scratch_bytes = 0;
+    unsigned sets = 0;
+};
 
 } // namespace bild

@@ -1,7 +1,8 @@
 // Gradient of the exact evidence of GenericGaussianModel (include/bild_amd.h, "evidence sensitivities"; DESIGN.md section
-// 20): the refusals, the chunks of whole trajectories, the segment recursion's launches and its formulas on the last column
-// of the forward table (gauss_segdp.h: the functions gauss_segdp.cpp calls, so that logev is the same number), the weight
-// table and the weighted tangent jobs (gauss_segtangent.h).  Kernels: gauss_segsens.hip.
+// 20): the forward and backward passes of the segment recursion and its formulas on the last column of the forward table
+// through SegdpCall (gauss_segdp.h), as bild_gauss_segment_evidence runs them, so that logev is the same number; the
+// posterior over k, the call's own weight table and the weighted tangent jobs (gauss_segtangent.h).  Kernels:
+// gauss_segsens.hip.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -14,16 +15,14 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
                                                 const uint8_t *transitions, unsigned flags, const double *log_k_prior, int P,
                                                 const bild_gauss_derivs *dm, int64_t scratch_bytes, bild_segsens_out *out)
 {
-    int n_traj = 0;
-    const int *T = nullptr;
-    BILD_TRY(internal_gauss_set_lengths(m, ts, &n_traj, &T));
-    if (!out) return fail(BILD_ERR_INVALID, "out is NULL");
-    const int S = m->S;
+    SegdpCall rec;          // (both before the frame, with the host copies below: asynchronous copies use their vectors)
+    SegTangent tangent;
+    std::vector<double> coef, top;
     // (nothing here is padded to a T_max, so no trajectory is too long for it)
-    BILD_TRY(segdp_check_call(S, k_max, flags, transitions, scratch_bytes, n_traj, T, std::numeric_limits<int>::max()));
+    BILD_TRY(rec.check(m, ts, k_max, transitions, std::numeric_limits<int>::max(), flags, scratch_bytes, out));
+    const int n_traj = rec.n_traj, K = rec.K;
     if (n_traj == 0) return BILD_OK;
-    BILD_TRY(gauss_check_args(m, n_traj, T, x, 0, 1, nullptr, nullptr, nullptr, P, dm));
-    const int K = k_max + 1;
+    BILD_TRY(gauss_check_args(m, n_traj, rec.T, x, 0, 1, nullptr, nullptr, nullptr, P, dm));
     if (log_k_prior)
         for (int j = 0; j < n_traj; ++j) {
             bool any = false;
@@ -35,90 +34,51 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
             }
             if (!any) return fail(BILD_ERR_INVALID, "log_k_prior of trajectory %d is -inf everywhere", j);
         }
-    int Tm = 1;
-    for (int j = 0; j < n_traj; ++j) Tm = std::max(Tm, T[j]);
-    const bool omit = (flags & BILD_SEGDP_NAN_OMIT) != 0;
-    const int ld = Tm + 1;
-    const int64_t slot = (int64_t)K * S * ld, om_tri = gauss_w_per_state(Tm), om_slot = (int64_t)S * (om_tri + ld);
+    tangent.stage(m, n_traj, rec.T, x, P, dm);
 
-    SegTangent tangent;     // (before the frame: asynchronous copies read its vectors)
-    tangent.stage(m, n_traj, T, x, P, dm);
+    // the call's own tables: the weights, and the coefficient and scale of every k
+    SegsensWeights w{};
+    w.om_tri = gauss_w_per_state(rec.Tm);
+    w.om_slot = (int64_t)rec.S * (w.om_tri + rec.Tm + 1);
 
     CallFrame call;
-    BILD_TRY(call.open(m, ts));
+    BILD_TRY(rec.open(call, m, ts, kSegdpForward | kSegdpBackward, (w.om_slot + K + K) * 8));
     hipStream_t st = call.st;
-
-    // a trajectory's share of the chunk: the recursion's tables and the weight table
-    const int64_t per_traj = slot * (2 * (5 * 8 + 4) + 4 * 8) + om_slot * 8 + (int64_t)K * K * 8 + (int64_t)K * S * 40 + (int64_t)K * 16;
-    int chunk = 0;
-    BILD_TRY(call.chunk_of(per_traj, scratch_bytes, n_traj, &chunk));
-
-    SegdpParams p{};
-    SegsensWeights w{};
-    uint8_t *d_tr = nullptr;
+    const int chunk = rec.chunk;
+    BILD_TRY(call.alloc(&w.omega, (size_t)chunk * w.om_slot));
     double *d_coef = nullptr, *d_top = nullptr;
-    BILD_TRY(call.alloc(&d_tr, (size_t)S * S));
-    BILD_TRY(alloc_fwd(call, &p.A, (size_t)chunk * slot));
-    BILD_TRY(alloc_fwd(call, &p.alpha, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.map_seg_start, (size_t)chunk * K * K));
-    BILD_TRY(call.alloc(&p.map_seg_state, (size_t)chunk * K * K));
-    BILD_TRY(call.alloc(&p.fin, (size_t)chunk * K * S * 5));
-    BILD_TRY(call.alloc(&p.beta.M, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.beta.Z, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.gamma.M, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&p.gamma.Z, (size_t)chunk * slot));
-    BILD_TRY(call.alloc(&w.omega, (size_t)chunk * om_slot));
     BILD_TRY(call.alloc(&d_coef, (size_t)chunk * K));
     BILD_TRY(call.alloc(&d_top, (size_t)chunk * K));
-    HIP_TRY(hipMemcpyAsync(d_tr, transitions, (size_t)S * S, hipMemcpyHostToDevice, st));
-    p.tr = d_tr;
-    p.slot = slot;
-    p.S = S;
-    p.K = K;
-    p.Tm = Tm;
-    p.ld = ld;
-    p.ntile = (Tm + kSegdpTile - 1) / kSegdpTile;
     w.coef = d_coef;
     w.top = d_top;
-    w.om_slot = om_slot;
-    w.om_tri = om_tri;
-
     BILD_TRY(tangent.upload(call));
     BILD_TRY(tangent.reserve(call, chunk));
 
-    const std::vector<long double> ntraces = trace_counts(S, transitions, K);
-    std::vector<double> fin((size_t)chunk * K * S * 5), coef((size_t)chunk * K), top((size_t)chunk * K);
+    coef.resize((size_t)chunk * K);
+    top.resize((size_t)chunk * K);
     std::vector<char> is_nan(chunk);
     const double nan = std::numeric_limits<double>::quiet_NaN(), ninf = -std::numeric_limits<double>::infinity();
 
     for (int j0 = 0; j0 < n_traj; j0 += chunk) {
         const int nc = std::min(chunk, n_traj - j0);
-        p.trajs = call.d_trajs + j0;
-        p.n_traj = nc;
-        BILD_TRY(segdp_run_forward(p, k_max, st));
-        BILD_TRY(segdp_run_backward(p, k_max, st));
-        HIP_TRY(hipMemcpyAsync(fin.data(), p.fin, (size_t)nc * K * S * 5 * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        BILD_TRY(rec.run(call, call.d_trajs + j0, nc));
+        BILD_TRY(rec.read_back(call, nc));
 
-        // logev of every k (segdp_evidence), the posterior over k, and the scale of every k's weights
+        // logev of every k, the posterior over k, and the scale of every k's weights
         for (int i = 0; i < nc; ++i) {
-            const int jt = j0 + i, Tj = T[jt];
-            std::vector<double> logev(K), zk(K), lw(K);
+            const int jt = j0 + i;
+            std::vector<double> zk(K), lw(K);
             bool bad_traj = false;
             double lmax = ninf;
-            for (int k = 0; k < K; ++k) {
-                const SegdpEvidence e =
-                    segdp_evidence(fin.data() + ((size_t)i * K + k) * S * 5, S, binom_ld(Tj - 1, k) * ntraces[k], omit);
-                const double le = e.logev;
-                logev[k] = le;
+            rec.each_k(i, rec.T[jt], [&](int k, const SegdpEvidence &e) {
                 zk[k] = e.z;
                 top[(size_t)i * K + k] = e.top;
                 const double lp = log_k_prior ? log_k_prior[(size_t)jt * K + k] : 0.0;
-                lw[k] = lp > ninf ? lp + le : ninf;     // a k of prior weight 0 does not count, NaN or not
+                lw[k] = lp > ninf ? lp + e.logev : ninf;    // a k of prior weight 0 does not count, NaN or not
                 if (std::isnan(lw[k])) bad_traj = true;
                 else lmax = std::max(lmax, lw[k]);
-                if (out->logev) out->logev[(size_t)jt * K + k] = le;
-            }
+                if (out->logev) out->logev[(size_t)jt * K + k] = e.logev;
+            });
             // pi normalised over k: log sum_k pi_k ev_k = lmax + log sum exp(lw - lmax) - log sum exp(log_k_prior)
             double tot = 0.0, lpmax = ninf, ptot = 0.0;
             for (int k = 0; k < K; ++k) lpmax = std::max(lpmax, log_k_prior ? log_k_prior[(size_t)jt * K + k] : 0.0);
@@ -137,8 +97,8 @@ extern "C" int bild_gauss_segment_sensitivities(const bild_gauss_model *m, const
         }
         HIP_TRY(hipMemcpyAsync(d_coef, coef.data(), (size_t)nc * K * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_top, top.data(), (size_t)nc * K * 8, hipMemcpyHostToDevice, st));
-        if (launch_segsens_weight(p, w, st)) return fail(BILD_ERR_HIP, "launch of the weight kernel failed");
-        BILD_TRY(tangent.run(call, j0, nc, is_nan.data(), w.omega, om_slot, om_tri, ld, out->exp_logl, out->grad, out->fisher));
+        if (launch_segsens_weight(rec.p, w, st)) return fail(BILD_ERR_HIP, "launch of the weight kernel failed");
+        BILD_TRY(tangent.run(call, j0, nc, is_nan.data(), w.omega, w.om_slot, w.om_tri, rec.p.ld, out->exp_logl, out->grad, out->fisher));
     }
     return BILD_OK;
 }
