@@ -3,6 +3,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#if defined(__HIPCC__)
+#define BILD_HD __host__ __device__
+#else
+#define BILD_HD
+#endif
+
 namespace bild {
 
 constexpr int kDMax = 3;      // mean vectors ONE task carries (the reference default is d = 3, models.py:222)
@@ -52,6 +58,7 @@ struct TrajDesc {
                              // steady-state innovation variance of the chain (see logl_kernel: convergence check)
     int64_t trans0;          // first entry of this trajectory in the transient table
     int64_t strans0;         // first record of this trajectory in the transient state table
+    int64_t pstrans0;        // first entry of this trajectory in the pair state table (entries, see pair_state_record)
 };
 
 // Transient table (vector kernels, modal path, beside the prefix table): entry of (trajectory, chain e, old state s, new
@@ -93,6 +100,23 @@ constexpr int prefix_record_doubles(int NP) { return (NP + kDMax) * NP + kDMax +
 //   (strans0 + (((e * S + s) * (S - 1) + (sn - (sn > s))) * T + t)) * snq + (g - 1) / sstride.
 constexpr int kStateGap = 255;  // largest gap that can ever be covered (BILD_STATES_MAX_GAP: 128 by default)
 constexpr int kStateStride = 3; // BILD_STATES_STRIDE
+// Pair state table (the second level of the state table).  The candidates that build the pair table run s -> sn at t1 and
+// sn -> sm at t2 = t1 + g1 -- exactly what a candidate with these two switches runs until its THIRD switch.  They leave their state
+// after g2 = 1, 1 + pstride, ... < pgap frames behind t2 (the prefix table's record layout, accumulators included, in the basis of
+// sm), and a chain of three and more close switches starts at its third switch from the last record at or in front of it.
+// Compact: no slots for sn == s or sm == sn, gaps g1 = 1 .. G - 1 (G: the pair table's gap_max), pnq records per entry.
+//   pstrans0 = (S - 1)^2 x the trajectory's first prefix record;  THE index, for the builders and for begin_chain alike:
+constexpr int kPairStateStride = 3; // BILD_PAIR_STATES_STRIDE
+BILD_HD inline int64_t pair_state_record(int64_t pstrans0, int S, int T, int G, int pnq, int e, int s, int sn, int sm, int t1, int g1, int q2)
+{
+    const int64_t sw = (((int64_t)e * S + s) * (S - 1) + (sn - (sn > s ? 1 : 0))) * (S - 1) + (sm - (sm > sn ? 1 : 0));
+    return ((pstrans0 + sw * T + t1) * (G - 1) + (g1 - 1)) * pnq + q2;
+}
+// ... and the records of a set of `prefix_records` prefix records (every trajectory, chain, state and frame)
+BILD_HD inline int64_t pair_state_records(int64_t prefix_records, int S, int G, int pnq)
+{
+    return prefix_records * (S - 1) * (S - 1) * (G - 1) * pnq;
+}
 
 struct KParams {
     const double *states; // S state blocks
@@ -131,6 +155,11 @@ struct KParams {
     double *strans_dump;      // non-null: this launch (the one that builds the transient table) also fills the state table
     int32_t sgap;             // gaps 1 .. sgap - 1 behind a switch are covered ...
     int32_t sstride, snq;     // ... by a record for every sstride-th of them (g = 1 + q * sstride, q < snq records per switch)
+    // pair state table: a chain of three and more close switches starts at its THIRD switch (first gap < gap_max)
+    const double *pstrans;
+    double *pstrans_dump;     // non-null: this launch (the one that builds the pair table) also fills the pair state table
+    int32_t pgap;             // gaps 1 .. pgap - 1 behind the second switch are covered ...
+    int32_t pstride, pnq;     // ... by a record for every pstride-th of them (g2 = 1 + q2 * pstride, q2 < pnq records per entry)
     // first-order tail (tail.hip): per prefix record kDMax x NP doubles g -- what a deviation of the means from the record does to
     // the log-likelihood of all later frames; null: a transient is run until its means have converged too
     const double *tail_g;

@@ -47,6 +47,8 @@ void load(Config &c)
     num("BILD_STATES_MAX_BYTES", c.states_max_bytes);
     num("BILD_STATES_STRIDE", c.states_stride);
     num("BILD_STATES_MAX_GAP", c.states_max_gap);
+    flag("BILD_NO_PAIR_STATES", c.no_pair_states);
+    num("BILD_PAIR_STATES_STRIDE", c.pair_states_stride);
     num("BILD_PAIRS_MAX_GAP", c.pairs_max_gap);
     if (c.pairs_max_gap < 2) c.pairs_max_gap = 2;
     num("BILD_PAIRS_MAX_TASKS", c.pairs_max_tasks);

@@ -21,6 +21,8 @@ struct Config {
     int64_t states_max_bytes = -1;                // BILD_STATES_MAX_BYTES  (-1: 4 GB, 64 GB for sets declared for >= 1e8 evaluations)
     int states_max_gap = 128;                     // BILD_STATES_MAX_GAP    largest gap the state table covers (<= 255; 64 until round 4)
     int states_stride = 3;                        // BILD_STATES_STRIDE     the state table keeps every n-th gap (1 ... 8)
+    bool no_pair_states = false;                  // BILD_NO_PAIR_STATES    no pair state table (the second level of the state table)
+    int pair_states_stride = 3;                   // BILD_PAIR_STATES_STRIDE  the pair state table keeps every n-th gap (1 ... 8)
     int pairs_max_gap = 128;                      // BILD_PAIRS_MAX_GAP
     int64_t pairs_max_tasks = (int64_t)40 << 20;  // BILD_PAIRS_MAX_TASKS
     // launches

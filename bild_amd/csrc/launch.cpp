@@ -146,6 +146,7 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
             p.tail_margin = std::max(0, config().tail_margin);
             const bool read_states = !config().no_states && !(flags & BILD_NO_STATES);
             bool states = false; // the launch fills or reads the transient state table
+            bool pair_states = false; // ... the pair state table (BILD_NO_STATES and the flag switch both levels off)
             if (building == LaunchIn::kFillTransients) {
                 p.trans_dump = ts.d_trans;
                 p.strans_dump = ts.d_strans;
@@ -155,10 +156,13 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
                 p.gap_max = ts.gap_max;
                 if (read_states) p.strans = ts.d_strans;
                 states = read_states;
+                p.pstrans_dump = ts.d_pstrans;
+                pair_states = ts.d_pstrans != nullptr;
             } else if (p.prefix && !p.no_jump) {
                 // (the state table as it was when the launch began: one that ensure_transients builds below is read from the next on)
                 states = read_states && ts.trans_state == 1;
                 if (states) p.strans = ts.d_strans;
+                pair_states = read_states && ts.trans2_state == 1;
                 if (ts.trans_state == 0) ensure_transients(m, ts, st);
                 if (ts.trans_state == 1) {
                     p.trans = ts.d_trans;
@@ -168,6 +172,9 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
                         p.trans2 = ts.d_trans2;
                         p.gap_max = ts.gap_max;
                     }
+                    // (as above: the table as it was when the launch began)
+                    if (pair_states && p.trans2 && !config().no_pair_states) p.pstrans = ts.d_pstrans;
+                    pair_states = p.pstrans != nullptr;
                     if (walk_fits(geom, lds)) {
                         p.walk_lds = 1;
                         lds += walk_bytes(geom);
@@ -178,6 +185,11 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
                 p.sgap = ts.sgap;
                 p.sstride = ts.sstride;
                 p.snq = ts.snq;
+            }
+            if (pair_states) {
+                p.pgap = ts.pgap;
+                p.pstride = ts.pstride;
+                p.pnq = ts.pnq;
             }
         }
         if (timing) p.frames_run = m.d_frames;

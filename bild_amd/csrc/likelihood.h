@@ -191,6 +191,9 @@ struct bild_trajset {
     mutable int64_t strans_entries = 0;   // (trajectory, chain, old state, new state, frame) combinations
     mutable int sgap = kStateGap;         // gaps 1 .. sgap - 1 behind a switch are covered (sized when the table is built) ...
     mutable int sstride = kStateStride, snq = 0; // ... by snq records per entry, one for every sstride-th gap
+    mutable double *d_pstrans = nullptr;  // pair state table (common.h), filled by the launch that builds the pair table
+    mutable int64_t pstrans_records = 0;  // records of the pair state table as built: prefix_records (S - 1)^2 (gap_max - 1) pnq
+    mutable int pgap = 0, pstride = kPairStateStride, pnq = 0; // gaps 1 .. pgap - 1 behind the second switch, every pstride-th
     mutable int trans_m_max = 0;          // longest converged transient of the single table
     mutable int two_switch_covered = 0;  // every candidate of <= 2 switches comes out of the tables (checked on the device when the pair table is built)
     mutable int trans_m_typ = 48;         // typical frames-to-convergence of the table's entries (90th percentile): the scheduler's yardstick
@@ -224,7 +227,7 @@ struct LaunchIn {
     const int8_t *d_thetas = nullptr;
     int32_t *status = nullptr;   // [0] != 0: a row was not a point on the simplex, [1]: such a row
     // set by ensure_transients / ensure_pairs alone: this launch FILLS a table (kFillTransients: ts.d_trans and ts.d_strans,
-    // kFillPairs: ts.d_trans2) instead of reading it -- an argument of this internal call, so that no ABI caller can ask for it
+    // kFillPairs: ts.d_trans2 and ts.d_pstrans) instead of reading it -- an argument of this internal call, so that no ABI caller can ask for it
     enum Fill { kFillNone, kFillTransients, kFillPairs } fill = kFillNone;
 };
 int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1, const int32_t *d_seg_start,

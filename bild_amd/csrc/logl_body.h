@@ -18,9 +18,9 @@
 // pointers (px, pprobe).  s2 and the switch the segment began with are NOT: they live in the row's LDS constants (row_const), and
 // whatever else a lambda captures costs registers across the loop -- two more cost the geometries short of them a round of spills.
 //
-// Code that runs only in table-building launches: write_record with dump (DUMP: the prefix table) and dump_state (BUILD: the state
-// table) in the general frame loop, and the transient / pair entry written in the epilogue (BUILD).  None of it is compiled into
-// the lean loop.
+// Code that runs only in table-building launches: write_record with dump (DUMP: the prefix table) and dump_state / dump_pair_state
+// (BUILD: the state tables) in the general frame loop, and the transient / pair entry written in the epilogue (BUILD).  None of it
+// is compiled into the lean loop.
 //
 // The LDS of a workgroup is laid out by LdsLayout (common.h), for this function, logl_one_kernel / walk_one and the host alike.
 #pragma once
@@ -901,6 +901,8 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
         // the transient state table (common.h) it begins at its SECOND switch instead: the state the first transient has
         // reached there, accumulators included, is a record of the table -- written by the candidate that built the transient
         // table's entry for this switch, which ran the very same frames from the very same record.
+        // (the walk plan, below: the task's table entries are in LDS, lane by lane)
+        const bool planned = use_transients && p.walk_lds != 0 && seg_in_lds;
         auto begin_chain = [&](int t_ptr) {
             if constexpr (JUMP) {
                 if (p.strans != nullptr && seg_in_lds && seg + 2 < nseg) {
@@ -912,11 +914,29 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                         const int q = (g1 - 1) / p.sstride, g0 = 1 + q * p.sstride;
                         const int64_t entry = (((int64_t)e * S + s) * (S - 1) + (sn - (sn > s ? 1 : 0))) * T + t;
                         const double *__restrict__ rec = p.strans + ((td->strans0 + entry) * p.snq + q) * REC;
-                        ++seg; // the segment of sn: the frame at t2 moves on to the next one
-                        note_switch(s, t);
-                        s = sn;
-                        next_start = t2;
-                        t += g0;
+                        // (the switch the run begins behind, the state it runs in, its next switch and its first frame)
+                        int links = 1, s_from = s, t_from = t, s_to = sn, t_next = t2, t_go = t + g0;
+                        // With the pair state table (common.h) it begins at its THIRD switch, where the task's prologue has found
+                        // that it may (below: "pair state starts"): the plan then holds -1 in place of the pair entry's frame
+                        // count, and the record and the frame to go on at in place of its value -- two LDS reads and the same
+                        // start, no index arithmetic beside the values the frame loop carries
+                        if constexpr (!BUILD) {
+                            if (planned && __double2hiint(walk[3 * (seg + 1) + 2]) == -1) {
+                                const double at = walk[3 * (seg + 1) + 1];
+                                rec = p.pstrans + (int64_t)__double2hiint(at) * REC;
+                                links = 2;
+                                s_from = sn;
+                                t_from = t2;
+                                s_to = seg_state_of(seg + 2);
+                                t_next = seg_start_of(seg + 3);
+                                t_go = __double2loint(at);
+                            }
+                        }
+                        seg += links; // the segment of sn (sm): the frame at t2 (t3) moves on to the next one
+                        note_switch(s_from, t_from);
+                        s = s_to;
+                        next_start = t_next;
+                        t = t_go;
                         start_from(rec, t, true, t_ptr);
                         return;
                     }
@@ -930,7 +950,6 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
         // sums of the new state's filter up to the switch behind.  Lane i - 1 of the task fetches those of switch i, all at
         // once, and leaves the two sums and the two frame counts in LDS; `land` then walks from switch to switch without
         // waiting for memory (four switches: 6.6 -> ~2 us of a task's life; the same numbers, added in the same order).
-        const bool planned = use_transients && p.walk_lds != 0 && seg_in_lds;
         if (planned && !handed) {
             for (int i = 1 + gl; i < nseg; i += (BLK || ROW) ? 16 : G) {
                 const int ti = seg_lds[i], s0 = seg_lds[kSegLds + i - 1], s1 = seg_lds[kSegLds + i];
@@ -974,6 +993,41 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                 walk[0] = record_of(seg_lds[kSegLds], t1 - 1)[kRecL];
             }
             wave_lds_fence();
+        }
+        // Pair state starts.  With the pair state table (common.h) a chain of three and more close switches t1 < t2 < t3 begins at
+        // its THIRD switch: the candidate that built the pair entry (t1, g1 = t2 - t1) ran the frames of the gap t2 .. from the
+        // same record, through the same code, and left its state behind every pstride-th of them.  Lane i - 1 decides for a
+        // chain that begins at switch i -- out of line of the frame loop, from the list and the plan in LDS alone -- and taken
+        // it is only where this candidate, started at its second switch, would run EVERY frame up to t3 and end no piece there:
+        //  (a) a record exists: g1 inside the pair table (and the first level's gaps), g2 = t3 - t2 inside the covered gaps;
+        //  (b) t3 - t1 < m_pair, the pair entry's frame count (hi word of the plan's third slot).  The builder's first look that
+        //      converged was the one at frame t1 + m_pair (m_pair = T - t1: none did), and it had written the records of all
+        //      frames up to there.  Its looks are this candidate's looks -- same states, same records, same schedule --, so none
+        //      of them at a frame <= t3 converges by the full criterion; equality is left out: a look AT t3 comes in front of
+        //      the switch.  (`land` cannot take the pair entry either: it would need t1 + m_pair <= t3);
+        //  (c) none of them takes a first-order tail: compare_with_table takes one only if t3 - t2 >= m_ref + tail_margin, m_ref > 0
+        //      the single entry of the switch at t2 (lo word of switch i + 1's third slot).
+        // The looks in the gap then do nothing but schedule the next look, and the switch at t3 schedules its own.  Where all
+        // hold, the plan's pair slots of switch i change their meaning: frame count -1 (`land` reads: no pair entry to take), and
+        // in place of the value the record (hi word; ensure_pairs keeps their number below 2^31) and the frame to go on at.
+        if constexpr (JUMP && !BUILD) {
+            if (planned && p.pstrans != nullptr && p.strans != nullptr) { // (begin_chain: a branch of the first level's start)
+                for (int i = 1 + gl; i + 2 < nseg; i += (BLK || ROW) ? 16 : G) {
+                    const int s0 = seg_lds[kSegLds + i - 1], sn = seg_lds[kSegLds + i], sm = seg_lds[kSegLds + i + 1];
+                    const int t1 = seg_lds[i], t2 = seg_lds[i + 1], t3 = seg_lds[i + 2];
+                    const int g1 = t2 - t1, g2 = t3 - t2;
+                    const double mm = walk[3 * i + 2];
+                    const int m_pair = __double2hiint(mm), m_ref = __double2loint(walk[3 * (i + 1) + 2]);
+                    const int q2 = (g2 - 1) / p.pstride;
+                    if (t1 >= 1 && sn != s0 && sm != sn && g1 >= 1 && g1 < p.gap_max && g1 < p.sgap && g2 >= 1 && g2 < p.pgap && q2 < p.pnq && g1 + g2 < m_pair &&
+                        (m_ref <= 0 || g2 < m_ref + p.tail_margin)) {
+                        const int64_t rec = pair_state_record(td->pstrans0, S, T, p.gap_max, p.pnq, e, s0, sn, sm, t1, g1, q2);
+                        walk[3 * i + 1] = __hiloint2double((int)rec, t2 + 1 + q2 * p.pstride);
+                        walk[3 * i + 2] = __hiloint2double(-1, __double2loint(mm));
+                    }
+                }
+                wave_lds_fence();
+            }
         }
         // at a synchronised point in front of frame t (== next_start, or T): take whatever the tables hold
         auto land = [&]() {
@@ -1082,6 +1136,20 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                                                                  (seg_state_of(1) - (seg_state_of(1) > seg_state_of(0) ? 1 : 0))) * T + t_switch) * p.snq
                                                : 0;
         auto dump_state = [&](int g) { write_record(p.strans_dump + (state_rec0 + g) * REC); };
+        // this launch builds the pair table and, beside it, the pair state table (common.h): tasks have three segments, the state
+        // after every pstride-th frame behind the second switch goes to its record.  Everything is read from the list in LDS at
+        // the frame of a record: nothing of it lives across the frame loop (see note_switch)
+        auto dump_pair_state = [&](int tt) {
+            if constexpr (BUILD && !kLean) {
+                if (p.pstrans_dump == nullptr || K1 != 3 || nseg != 3 || !seg_in_lds || tt >= T) return;
+                const int t1 = seg_start_of(1), t2 = seg_start_of(2), g1 = t2 - t1, g2 = tt - t2;
+                if (g2 < 1 || g2 >= p.pgap || (g2 - 1) % p.pstride != 0) return;
+                const int q2 = (g2 - 1) / p.pstride;
+                const int s0 = seg_state_of(0), sn = seg_state_of(1), sm = seg_state_of(2);
+                if (g1 < 1 || g1 >= p.gap_max || q2 >= p.pnq || sn == s0 || sm == sn) return;
+                write_record(p.pstrans_dump + pair_state_record(td->pstrans0, S, T, p.gap_max, p.pnq, e, s0, sn, sm, t1, g1, q2) * REC);
+            }
+        };
         if constexpr (DUMP) dump(0);
         // A comparison with the table is due at frame t (the state after frame t - 1 against the table's record): either the
         // next look is scheduled, or the own piece ends here and the task goes on at its next synchronised point.
@@ -1314,6 +1382,7 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                 if constexpr (JUMP) {
                     if (dump_states && t < T && t - t_switch < p.sgap && (t - t_switch - 1) % p.sstride == 0)
                         dump_state((t - t_switch - 1) / p.sstride);
+                    dump_pair_state(t);
                 }
                 if (JUMP && jumping && t == t_check && t < T) {
                     if (compare_with_table()) break;

@@ -396,6 +396,26 @@ int ensure_pairs(const bild_model &m, const bild_trajset &ts, hipStream_t st)
     TransEntry *d_tab;
     LaunchIn in;
     in.fill = LaunchIn::kFillPairs;
+    // The pair state table (common.h), filled by the same launch: the second level of the state table, gated like the first and
+    // from the same byte budget (ensure_transients), of which the first level has taken its share.  It is built whole or not at
+    // all: what it saves is the second gap of a launch's longest chain, and short gaps alone do not shorten that chain.
+    double *d_pstates = nullptr;
+    int pgap = 0, pnq = 0;
+    const int pstride = std::max(1, std::min(config().pair_states_stride, 8));
+    if (!config().no_states && !config().no_pair_states && ts.d_strans != nullptr) {
+        const size_t rec_bytes = (size_t)prefix_record_doubles(m.NPm[kModal]) * sizeof(double);
+        pgap = std::min<int>(std::max(2, std::min(config().states_max_gap, 255)), ts.trans_m_max + 1);
+        pnq = (pgap - 2) / pstride + 1; // records for g2 = 1, 1 + pstride, ... <= pgap - 1
+        const size_t pbytes = pair_state_records(ts.prefix_records, S, G, pnq) * rec_bytes;
+        size_t budget = (size_t)std::max<int64_t>(config().states_max_bytes, 0);
+        if (config().states_max_bytes < 0) budget = ts.expected_evals >= (int64_t)100000000 ? ((size_t)64 << 30) : ((size_t)4 << 30);
+        const size_t first_level = (size_t)ts.strans_records * rec_bytes;
+        budget = budget > first_level ? budget - first_level : 0;
+        budget = std::min(budget, (free_b > bytes ? free_b - bytes : 0) / 3);
+        // (the walk plan holds a record's number in 32 bits: logl_body.h, "pair state starts")
+        const bool fits = pbytes <= budget && pair_state_records(ts.prefix_records, S, G, pnq) < ((int64_t)1 << 31);
+        if (!fits || !scratch.alloc(&d_pstates, pbytes)) d_pstates = nullptr;
+    }
     const bool ok = scratch.alloc(&d_desc, (size_t)7 * nb * sizeof(int32_t)) && scratch.alloc(&d_first, first.size() * sizeof(int64_t)) &&
                     scratch.alloc(&d_sink, (size_t)nb * sizeof(double)) && scratch.alloc(&d_tab, bytes) &&
                     hipMemsetAsync(d_tab, 0, bytes, st) == hipSuccess &&
@@ -404,9 +424,14 @@ int ensure_pairs(const bild_model &m, const bild_trajset &ts, hipStream_t st)
                     scratch.run([&] {
                         ts.d_trans2 = d_tab; // launch_batch passes it on as the table to FILL (trans2_state is still -1)
                         ts.gap_max = G;
+                        ts.d_pstrans = d_pstates; // (likewise; null: the entries alone)
+                        ts.pgap = pgap;
+                        ts.pstride = pstride;
+                        ts.pnq = pnq;
                         return launch_batch(m, ts, nb, 3, d_desc, d_desc + 3 * nb, d_desc + 6 * nb, nullptr, BILD_PATH_MODAL, st, d_sink, in) == BILD_OK;
                     }, &ts.trans2_build_ms);
     ts.d_trans2 = nullptr;
+    ts.d_pstrans = nullptr;
     if (!ok) return BILD_OK; // (`first` is read by an asynchronous copy: declared before `scratch`, it outlives its synchronisation)
     // do the tables cover every candidate of at most two switches?  (schedule.hip: two_switch_cover_kernel)
     std::vector<int64_t> ent((size_t)ts.n_traj + 1, 0);
@@ -422,6 +447,8 @@ int ensure_pairs(const bild_model &m, const bild_trajset &ts, hipStream_t st)
                       hipMemcpy(&cov, d_cov, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
     ts.two_switch_covered = good && cov == 1 ? 1 : 0;
     ts.d_trans2 = scratch.keep(d_tab);
+    ts.d_pstrans = scratch.keep(d_pstates);
+    ts.pstrans_records = d_pstates ? pair_state_records(ts.prefix_records, S, G, pnq) : 0;
     ts.trans2_entries = entries;
     ts.trans2_state = 1;
     return BILD_OK;
@@ -549,6 +576,7 @@ int bild_trajset_create(const bild_model *m, int n_traj, const int32_t *T, const
             ts->descs[j].prefix_rec0 = rec;
             ts->descs[j].trans0 = rec * m->S; // S entries (one per new state) for every prefix record
             ts->descs[j].strans0 = rec * (m->S - 1); // S - 1 switches (one per OTHER state) for every prefix record
+            ts->descs[j].pstrans0 = rec * (m->S - 1) * (m->S - 1); // ... and S - 1 second switches for each of them
             rec += (int64_t)T[j] * m->S * ts->dstar_max;
         }
         ts->strans_entries = rec * (m->S - 1);
@@ -587,6 +615,7 @@ int bild_trajset_destroy(bild_trajset *ts)
     tab_free(ts->d_trans);
     tab_free(ts->d_trans2);
     tab_free(ts->d_strans);
+    tab_free(ts->d_pstrans);
     delete ts;
     return BILD_OK;
 }
@@ -599,7 +628,8 @@ int bild_prefix_info(const bild_trajset *ts, int64_t *bytes, double *build_ms)
         *bytes = (built ? ts->prefix_records * prefix_record_doubles(ts->model->NPm[kModal]) * (int64_t)sizeof(double) : 0) +
                  (trans ? ts->trans_entries * (int64_t)sizeof(TransEntry) : 0) +
                  (pairs ? ts->trans2_entries * (int64_t)sizeof(TransEntry) : 0) +
-                 (trans && ts->d_strans ? ts->strans_records * prefix_record_doubles(ts->model->NPm[kModal]) * (int64_t)sizeof(double) : 0);
+                 (trans && ts->d_strans ? ts->strans_records * prefix_record_doubles(ts->model->NPm[kModal]) * (int64_t)sizeof(double) : 0) +
+                 (pairs && ts->d_pstrans ? ts->pstrans_records * prefix_record_doubles(ts->model->NPm[kModal]) * (int64_t)sizeof(double) : 0);
     if (build_ms)
         *build_ms = (built ? ts->prefix_build_ms : 0.0) + (trans ? ts->trans_build_ms : 0.0) + (pairs ? ts->trans2_build_ms : 0.0);
     return BILD_OK;

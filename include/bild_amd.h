@@ -78,7 +78,10 @@ typedef enum bild_status {
  * a chain can start with -- up to the set's longest converged transient, measured when the transient table is built -- and
  * costs ~100 MB per 1000 frames of a 2-state trajectory: it is built for sets that need at most 4 GB of it, 64 GB for sets
  * declared for >= 1e8 evaluations with bild_trajset_expect, BILD_STATES_MAX_BYTES=<n> otherwise; at most a third of the free
- * memory in any case.) */
+ * memory in any case.  The same budget, after the first level's share, holds the PAIR state table -- the states the builders
+ * of the pair table leave behind their second switch, from which a chain of three and more close switches starts at its third
+ * switch: ~2 GB per 1000 frames of a 2-state trajectory, built whole or not at all; BILD_NO_PAIR_STATES=1,
+ * BILD_PAIR_STATES_STRIDE=<n>.  The flag and BILD_NO_STATES switch both levels off.) */
 #define BILD_NO_STATES 0x100u
 
 /* Do not leave a transient on the first-order tail (csrc/tail.hip: once the covariance of a candidate's filter has converged
