@@ -182,6 +182,9 @@ _SIGNATURES = {
     # expected segment-length counts under a dwell-time prior (gauss_dwelllen.cpp)
     'bild_gauss_dwell_lengths': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_uint, ctypes.c_int64,
                                                 _vp]),
+    # exact online filtering under a dwell-time prior (gauss_dwellfilt.cpp)
+    'bild_gauss_dwell_filter': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
+                                               ctypes.c_int64, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1439,6 +1442,29 @@ def gauss_dwell_lengths(model, ts, log_init, log_jump, log_dwell, log_surv, omit
     spec = DwellLengthsOut(**{name: aptr(a) for name, a in res.items()})
     check(lib().bild_gauss_dwell_lengths(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
                                          DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
+    return res
+
+
+class DwellFilterOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'prefix_logev', 'log_filtered', 'run_mean', 'log_run', 'n_nan_windows')]
+
+
+def gauss_dwell_filter(model, ts, log_init, log_jump, log_dwell, log_surv, run_max=0, omit=False, scratch_bytes=0):
+    """
+    exact online filtering under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_filter): a dict of logev
+    (n_traj,), prefix_logev and run_mean (n_traj, T_max), log_filtered (n_traj, S, T_max), n_nan_windows (n_traj, T_max) int64
+    and, with run_max > 0, log_run (n_traj, S, T_max, run_max) (None without); T_max the set's longest trajectory
+    """
+    S = model.S
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
+    n, R = ts.n_traj, int(run_max)
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty(n), 'prefix_logev': np.empty((n, T_max)), 'log_filtered': np.empty((n, S, T_max)),
+           'run_mean': np.empty((n, T_max)), 'log_run': np.empty((n, S, T_max, R)) if R > 0 else None,
+           'n_nan_windows': np.empty((n, T_max), dtype=np.int64)}
+    spec = DwellFilterOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
+    check(lib().bild_gauss_dwell_filter(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max, R,
+                                        DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
     return res
 
 

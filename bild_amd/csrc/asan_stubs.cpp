@@ -119,6 +119,10 @@ int launch_dwellsens_weight(const DwellParams &, const DwellsensWeights &, void 
 namespace bild {
 int launch_dwell_lengths(const DwellParams &, const DwellLengths &, void *) { return 1; }
 }
+#include "gauss_dwellfilt.h"
+namespace bild {
+int launch_dwell_filter(const DwellParams &, const DwellFilter &, void *) { return 1; }
+}
 #include "gauss_dwelldraw.h"
 namespace bild {
 int launch_dwelldraw_head(const DwelldrawParams &, void *) { return 1; }

@@ -2,7 +2,7 @@
 // call and the rule that cuts the call into chunks.  exact.cpp opens one itself; the calls on the segment recursion and on
 // the dwell-time recursion declare one and have it opened by the recursion's owner (SegdpCall of gauss_segdp.h: gauss_segdp.cpp,
 // gauss_segdraw.cpp, gauss_segsens.cpp; DwellCall of gauss_dwell.h: gauss_dwell.cpp, gauss_dwelldraw.cpp, gauss_dwellsens.cpp,
-// gauss_dwelllen.cpp); gauss_segtangent.cpp and DrawGroups (gauss_draws.h) allocate through it.  Host only; private to the
+// gauss_dwelllen.cpp, gauss_dwellfilt.cpp); gauss_segtangent.cpp and DrawGroups (gauss_draws.h) allocate through it.  Host only; private to the
 // library.
 #pragma once
 #include "internal.h"

@@ -1,6 +1,6 @@
 // Exact inference under a dwell-time prior (include/bild_amd.h, "exact inference under a dwell-time prior"; DESIGN.md
 // section 21).  DwellCall is the host side of the recursion that bild_gauss_dwell_evidence here, gauss_dwellsens.cpp,
-// gauss_dwelllen.cpp and gauss_dwelldraw.cpp share (gauss_dwell.h): the refusals, the frame on the set's stream, the chunks
+// gauss_dwelllen.cpp, gauss_dwellfilt.cpp and gauss_dwelldraw.cpp share (gauss_dwell.h): the refusals, the frame on the set's stream, the chunks
 // of whole trajectories, the prior's upload, the tables, the kernels' parameters, the two passes, and the NaN rule on what
 // comes back.  Kernels: gauss_dwell.hip.
 #include <algorithm>

@@ -47,7 +47,7 @@ struct DwellParams {
     int n_traj, S, L, Tm, ld, ntile;
 };
 
-// ---- the host side that the calls on the recursion share (gauss_dwell.cpp; evidence, sensitivities, lengths, draws) ----
+// ---- the host side that the calls on the recursion share (gauss_dwell.cpp; evidence, sensitivities, lengths, filter, draws) ----
 struct CallFrame;
 
 // The per-trajectory tables of the recursion: the member of DwellParams (its element size is the table's), the set it

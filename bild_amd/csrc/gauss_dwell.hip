@@ -29,33 +29,7 @@ namespace {
 
 constexpr int kWaves = kDwellWaves;
 
-// (m, z) += exp(t): z counts in units of exp(m)
-__device__ __forceinline__ void lse_add(double &m, double &z, double t)
-{
-    if (!(t > neg_inf())) return;
-    if (t > m) {
-        z = z * exp(m - t) + 1.0;
-        m = t;
-    } else {
-        z += exp(t - m);
-    }
-}
-
-// (m, z) of two sums; the same bits whichever side is called first
-__device__ __forceinline__ void lse_merge(double &m, double &z, double m2, double z2)
-{
-    const double top = fmax(z > 0.0 ? m : neg_inf(), z2 > 0.0 ? m2 : neg_inf());
-    if (!(top > neg_inf())) {
-        m = neg_inf(), z = 0.0;
-        return;
-    }
-    const double u = z > 0.0 ? z * exp(m - top) : 0.0, v = z2 > 0.0 ? z2 * exp(m2 - top) : 0.0;
-    m = top;
-    z = u + v;
-}
-
-__device__ __forceinline__ double lse_value(double m, double z) { return z > 0.0 ? m + log(z) : neg_inf(); }
-
+// (lse_add, lse_merge, lse_value: wave.h)
 // log prior weight of a segment [a, b) in state s: the last segment is censored
 __device__ __forceinline__ double omega(const DwellParams &p, int s, int a, int b, int T)
 {

@@ -1,6 +1,7 @@
 // What the kernels of the exact-inference calls share (gauss_segdp.hip, gauss_segdraw.hip, gauss_segsens.hip, gauss_dwell.hip,
-// gauss_dwelldraw.hip, gauss_dwellsens.hip): the two constants, the reductions and scans across the 64 lanes of a wavefront, the step of an
-// inverse-CDF pick, the carry of the marginals and the uniforms of a draw.  Every function does its operations in one fixed
+// gauss_dwelldraw.hip, gauss_dwellsens.hip, gauss_dwellfilt.hip): the two constants, the reductions and scans across the 64 lanes of a
+// wavefront, the running sums of exponentials of the dwell-time recursion, the step of an inverse-CDF pick, the carry of the
+// marginals and the uniforms of a draw.  Every function does its operations in one fixed
 // order, so a kernel that calls it sums as the others do.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -42,6 +43,50 @@ __device__ __forceinline__ double wave_scan_down(double v, int lane)
         if (lane + off < 64) v += up;
     }
     return v;
+}
+
+// ---- sums of exponentials kept as (m, z): the sum is z exp(m) (gauss_dwell.hip, gauss_dwellfilt.hip) ----
+// (m, z) += exp(t): z counts in units of exp(m)
+__device__ __forceinline__ void lse_add(double &m, double &z, double t)
+{
+    if (!(t > neg_inf())) return;
+    if (t > m) {
+        z = z * exp(m - t) + 1.0;
+        m = t;
+    } else {
+        z += exp(t - m);
+    }
+}
+
+// (m, z) of two sums; the same bits whichever side is called first
+__device__ __forceinline__ void lse_merge(double &m, double &z, double m2, double z2)
+{
+    const double top = fmax(z > 0.0 ? m : neg_inf(), z2 > 0.0 ? m2 : neg_inf());
+    if (!(top > neg_inf())) {
+        m = neg_inf(), z = 0.0;
+        return;
+    }
+    const double u = z > 0.0 ? z * exp(m - top) : 0.0, v = z2 > 0.0 ? z2 * exp(m2 - top) : 0.0;
+    m = top;
+    z = u + v;
+}
+
+__device__ __forceinline__ double lse_value(double m, double z) { return z > 0.0 ? m + log(z) : neg_inf(); }
+
+// lse_add with a second sum on the same scale: r counts len * exp(t) in units of exp(m) and is rescaled together with z
+__device__ __forceinline__ void lse_add_len(double &m, double &z, double &r, double t, double len)
+{
+    if (!(t > neg_inf())) return;
+    if (t > m) {
+        const double e = exp(m - t);
+        z = z * e + 1.0;
+        r = r * e + len;
+        m = t;
+    } else {
+        const double e = exp(t - m);
+        z += e;
+        r += len * e;
+    }
 }
 
 // The wave's inverse-CDF pick among the entries b = lo .. hi of a list (lo >= 1), walked in blocks of 64 ascending b, lane = b;

@@ -28,6 +28,10 @@ with respect to model parameters; `GenericGaussianModel.fit_dwell` fits a model,
 `exact_dwell_lengths` (bild_gauss_dwell_lengths) is the gradient of that evidence with respect to the
 prior's own length tables: the expected number of segments of every length; `fit_dwell_prior` fits the dwell-time distributions
 themselves by EM on those counts, in the discrete-hazard parametrisation of `DwellPrior.from_hazard`.
+
+`exact_dwell_filter` (bild_gauss_dwell_filter) gives the causal answers under that prior: per frame the
+state probabilities, the run-length posterior and the evidence of the data so far, and from the latter the one-step predictive
+log-likelihoods.
 """
 import math
 import warnings
@@ -801,6 +805,76 @@ def exact_dwell(trajs, model, prior, marginals=True, nan='propagate', scratch_by
     res = _lib.gauss_dwell_evidence(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
                                     marginals=marginals, omit=nan == 'omit', scratch_bytes=scratch_bytes)
     out = _dwell_results(items, model, prior, nan, res)
+    return out[0] if single else out
+
+
+# ---------------------------------------------------------------- online filtering under the dwell-time prior (section 25)
+
+class DwellFilterResults:
+    """
+    `exact_dwell_filter` of one trajectory of T frames: at frame t, what `exact_dwell` says about the truncation x[:t + 1].
+
+    traj, model, prior, nan : as given
+    log_evidence : the evidence of the whole trajectory, `exact_dwell`'s number bit for bit
+    prefix_log_evidence : (T,) the evidence of x[:t + 1] under the same prior tables
+    log_predictive : (T,) `prefix_log_evidence[t] - prefix_log_evidence[t - 1]`, the first entry `prefix_log_evidence[0]`.
+        This is log p(x_t | x_0 ... x_{t-1}) ONLY for a prior whose tables are consistent under truncation:
+        `log_surv[s][l]` = log sum_{l' >= l} exp(`log_dwell[s][l']`) with normalised jumps, as `DwellPrior.markov` and
+        `DwellPrior.from_hazard` build them; the terms then add up to `log_evidence` frame by frame.  For other tables it is
+        only a difference of two evidences.
+    log_filtered : (S, T) log P(theta_t = s | x_0 ... x_t)
+    run_length_mean : (T,) the expected number of frames that the segment containing frame t has lasted, given x_0 ... x_t
+    log_run_length : (S, T, run_max) log P(theta_t = s, the current segment has lasted r frames | x_0 ... x_t) at [s, t, r - 1],
+        -inf for r > t + 1; None without `run_max`
+    n_nan_windows : (T,) `exact_dwell`'s `n_nan_windows` of x[:t + 1]
+
+    Under nan='propagate' every array is NaN at the frames with `n_nan_windows[t]` > 0 and untouched before; a frame whose
+    prefix has no profile of positive weight has `prefix_log_evidence` -inf and NaN elsewhere.
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'log_evidence', 'prefix_log_evidence', 'log_predictive', 'log_filtered',
+                 'run_length_mean', 'log_run_length', 'n_nan_windows')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return f"DwellFilterResults(T={len(self.traj)}, log_evidence={self.log_evidence!r})"
+
+
+def exact_dwell_filter(trajs, model, prior, run_max=0, nan='propagate', scratch_bytes=0):
+    """
+    Exact online (causal) inference for a `GenericGaussianModel` under a dwell-time prior: for every frame t the state
+    probabilities, the distribution of how long the current segment has lasted (the Bayesian online change-point quantity) and
+    the evidence given the data up to t alone, from the forward pass of `exact_dwell` and one more kernel without a
+    sequential chain (bild_gauss_dwell_filter).
+
+    trajs, model, prior, nan, scratch_bytes : as for `exact_dwell`; a list gives a list of results from ONE device call
+    run_max : run lengths r = 1 ... run_max kept in `log_run_length` (0: not computed; S x T x run_max doubles a trajectory)
+
+    Every refusal of `exact_dwell`, and a negative `run_max`, is raised before the trajectories are uploaded.  Returns
+    `DwellFilterResults` or a list of them.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    if int(run_max) != run_max or run_max < 0:
+        raise ValueError(f"run_max = {run_max!r}: an integer >= 0")
+    if not items:
+        return []
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_dwell_filter(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
+                                  run_max=int(run_max), omit=nan == 'omit', scratch_bytes=scratch_bytes)
+    out = []
+    for j, t in enumerate(items):
+        T = len(t)
+        prefix = res['prefix_logev'][j, :T].copy()
+        with np.errstate(invalid='ignore'):
+            predictive = np.diff(prefix, prepend=0.0)
+        out.append(DwellFilterResults(
+            traj=t, model=model, prior=prior, nan=nan, log_evidence=float(res['logev'][j]), prefix_log_evidence=prefix,
+            log_predictive=predictive, log_filtered=res['log_filtered'][j, :, :T].copy(), run_length_mean=res['run_mean'][j, :T].copy(),
+            log_run_length=None if res['log_run'] is None else res['log_run'][j, :, :T].copy(),
+            n_nan_windows=res['n_nan_windows'][j, :T].copy()))
     return out[0] if single else out
 
 

@@ -1135,6 +1135,50 @@ int bild_gauss_dwell_lengths(const bild_gauss_model *m, const bild_gauss_trajset
                              const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, unsigned flags,
                              int64_t scratch_bytes, bild_dwell_lengths_out *out);
 
+/* ---------------------------------------------------------------- exact online filtering under a dwell-time prior ----
+ * GenericGaussianModel only, at most 4 states.  The causal answers under the dwell-time prior of
+ * bild_gauss_dwell_evidence (same tables, same NaN flag): what that call says about the truncated trajectory x[:t + 1], for
+ * every frame t of every trajectory, from one forward pass.  With that block's alpha, for the prefix ends b = t + 1 = 1 .. T:
+ *   G(b, s) = log( e^(log_init[s] + log_surv[s][b] + F[s][b]) + sum_{c = 1 .. b - 1} e^(alpha(c, s) + log_surv[s][b - c] + W[s][c - 1][b]) )
+ *   E(b)    = log sum_s e^G(b, s)
+ * the forward sum at end frame b with the last segment censored.  A window's table entry depends on the data inside the
+ * window alone, so the tables of the whole trajectory serve every prefix.  Per trajectory of T frames:
+ *   logev          the evidence of the whole trajectory as bild_gauss_dwell_evidence gives it, bit for bit: the same kernel
+ *   prefix_logev   T_max: E(t + 1), the evidence of x[:t + 1] under the same tables
+ *   log_filtered   S x T_max: G(t + 1, s) - E(t + 1) = log P(theta_t = s | x_0 .. x_t)
+ *   run_mean       T_max: the expected length so far of the segment that contains frame t given x_0 .. x_t,
+ *                  sum_s sum_c (b - c) term / e^E(b), c = 0 for the first segment: a sum of non-negative terms
+ *   log_run        S x T_max x run_max: entry [s][t][r - 1] = log P(theta_t = s, the current segment has lasted r frames |
+ *                  x_0 .. x_t), the single term with c = b - r minus E(b), for r = 1 .. min(run_max, b); -inf where that term
+ *                  weighs 0 and -inf behind min(run_max, b).  A subtraction of logs: no exp
+ *   n_nan_windows  T_max: what bild_gauss_dwell_evidence reports as n_nan_windows of x[:t + 1]; 0 behind T
+ * Every other entry behind a trajectory's T is NaN.  prefix_logev[t] - prefix_logev[t - 1] is log p(x_t | x_0 .. x_{t-1}) only
+ * where the tables are consistent under truncation: log_surv[s][l] = log sum_{l' >= l} exp(log_dwell[s][l']) and normalised
+ * jumps; otherwise it is a difference of two evidences and no more.
+ * NaN windows: the kernel counts per end frame b the skipped windows [c, b) whose start is reachable (alphaArg >= 0; c = 0:
+ * log_init finite) under their log_surv weight, nG(b), and under their log_dwell weight, nA(b);
+ * n_nan_windows[t] = nG(t + 1) + sum_{e <= t} nA(e).  flags = 0 (BILD_DWELL_NAN_PROPAGATE): every output at a frame t with
+ * n_nan_windows[t] > 0 is NaN, earlier frames are untouched; logev follows bild_gauss_dwell_evidence.  BILD_DWELL_NAN_OMIT:
+ * the skipped windows weigh 0.  A prefix without a profile of positive weight has prefix_logev -inf and NaN in log_filtered,
+ * run_mean and the whole row of log_run at that frame.  The switches c are summed by eight waves, wave q taking c = 1 + q,
+ * 9 + q, .. in ascending order, the waves merged in wave order: no atomics, fixed summation orders that depend on the
+ * trajectory alone, so results are bit-identical across calls, the order of the set, a trajectory alone or in a batch,
+ * scratch_bytes (chunks of whole trajectories; 0: at most 1 GiB and a third of the free device memory) and whether log_run is
+ * asked for.  Refused before any device work: what bild_gauss_dwell_evidence refuses, run_max < 0, and log_run given with
+ * run_max = 0 (BILD_ERR_INVALID).  log_run == NULL: run_max is not used.  Plain launches on the set's stream.  Synchronous. */
+typedef struct bild_dwell_filter_out {
+    double *logev;                          /* n_traj */
+    double *prefix_logev;                   /* n_traj x T_max */
+    double *log_filtered;                   /* n_traj x S x T_max */
+    double *run_mean;                       /* n_traj x T_max */
+    double *log_run;                        /* n_traj x S x T_max x run_max */
+    int64_t *n_nan_windows;                 /* n_traj x T_max */
+} bild_dwell_filter_out;                    /* every pointer may be NULL: not written */
+
+int bild_gauss_dwell_filter(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
+                            const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, int run_max,
+                            unsigned flags, int64_t scratch_bytes, bild_dwell_filter_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,16 @@
 """
 Wall time of the exact inference under a dwell-time prior (bild_amd.exact_dwell) on the data of
 tools/segdp_bench.py (GenericGaussianModel, T = 1000 frames, S = 2, d = 3): one trajectory and a batch of 256, with the
-marginals and the expected counts, next to `exact_sample(k_max=20, marginals=True)` on the same data in the same session,
+marginals and the expected counts, the online filter `exact_dwell_filter` (without run lengths, and on
+the single trajectory with all of them) and `exact_sample(k_max=20, marginals=True)` on the same data in the same session,
 and one `fit_markov_prior` on 64 simulated trajectories of T = 200 (the data set of tests/test_gpu_dwell.py) with its number
 of device calls and the share of the one table build.  Each configuration runs once untimed (tables built, code loaded),
 then `--reps` times; the best wall time of a synchronous call is reported.  One JSON line per configuration.
 
     python tools/dwell_bench.py [--T 1000] [--kmax 20] [--batch 256] [--reps 5] [--single-only] [--out FILE]
 
-`--single-only` runs the single-trajectory `exact_dwell` alone: the part a `rocprofv3 --kernel-trace --stats` run is made of.
+`--single-only` runs the single-trajectory `exact_dwell` and `exact_dwell_filter` alone: the part a `rocprofv3 --kernel-trace
+--stats` run is made of.
 """
 import argparse
 import json
@@ -83,6 +85,13 @@ def main():
             report({'what': 'exact_dwell', 'n_traj': n, 'T': T, 'S': 2, 'd': 3, 'marginals': marg, 'seconds': best,
                     'trajectories_per_s': n / best, 'table_build_seconds': build, 'log_evidence': first.log_evidence,
                     'map_switches': int(np.count_nonzero(np.diff(first.map_profile[:])))})
+        for run_max in ([0, T] if n == 1 else [0]):
+            best, res = best_of(lambda: bild_amd.exact_dwell_filter(arg, model, prior, run_max=run_max), a.reps)
+            first = res if n == 1 else res[0]
+            report({'what': 'exact_dwell_filter', 'n_traj': n, 'T': T, 'S': 2, 'd': 3, 'run_max': run_max, 'seconds': best,
+                    'trajectories_per_s': n / best, 'table_build_seconds': build, 'log_evidence': first.log_evidence,
+                    'prefix_log_evidence_last': float(first.prefix_log_evidence[-1]),
+                    'run_length_mean_last': float(first.run_length_mean[-1])})
         if a.single_only:
             break
         best, res = best_of(lambda: bild_amd.exact_sample(arg, model, k_max=a.kmax, marginals=True), a.reps)
