@@ -185,6 +185,8 @@ _SIGNATURES = {
     # exact online filtering under a dwell-time prior (gauss_dwellfilt.cpp)
     'bild_gauss_dwell_filter': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
                                                ctypes.c_int64, _vp]),
+    'bild_gauss_dwell_lag': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
+                                            ctypes.c_int64, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1465,6 +1467,30 @@ def gauss_dwell_filter(model, ts, log_init, log_jump, log_dwell, log_surv, run_m
     spec = DwellFilterOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
     check(lib().bild_gauss_dwell_filter(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max, R,
                                         DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
+    return res
+
+
+DWELL_LAG_MAX = 63      # BILD_DWELL_LAG_MAX: a window of lag + 1 frames is one wavefront
+
+
+class DwellLagOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'log_lagged', 'n_nan_windows')]
+
+
+def gauss_dwell_lag(model, ts, log_init, log_jump, log_dwell, log_surv, lag, omit=False, scratch_bytes=0):
+    """
+    exact fixed-lag smoothing under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_lag): a dict of logev
+    (n_traj,), log_lagged (n_traj, S, T_max, lag + 1) and n_nan_windows (n_traj, T_max) int64; T_max the set's longest trajectory
+    """
+    S = model.S
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
+    n, lag = ts.n_traj, int(lag)
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty(n), 'log_lagged': np.empty((n, S, T_max, max(lag, 0) + 1)),
+           'n_nan_windows': np.empty((n, T_max), dtype=np.int64)}
+    spec = DwellLagOut(**{name: aptr(a) for name, a in res.items()})
+    check(lib().bild_gauss_dwell_lag(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max, lag,
+                                     DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
     return res
 
 

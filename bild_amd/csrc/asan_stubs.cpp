@@ -123,6 +123,11 @@ int launch_dwell_lengths(const DwellParams &, const DwellLengths &, void *) { re
 namespace bild {
 int launch_dwell_filter(const DwellParams &, const DwellFilter &, void *) { return 1; }
 }
+#include "gauss_dwelllag.h"
+namespace bild {
+int launch_dwell_lag_bases(const DwellParams &, const DwellLag &, void *) { return 1; }
+int launch_dwell_lag_windows(const DwellParams &, const DwellLag &, void *) { return 1; }
+}
 #include "gauss_dwelldraw.h"
 namespace bild {
 int launch_dwelldraw_head(const DwelldrawParams &, void *) { return 1; }

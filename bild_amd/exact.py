@@ -32,6 +32,9 @@ themselves by EM on those counts, in the discrete-hazard parametrisation of `Dwe
 `exact_dwell_filter` (bild_gauss_dwell_filter) gives the causal answers under that prior: per frame the
 state probabilities, the run-length posterior and the evidence of the data so far, and from the latter the one-step predictive
 log-likelihoods.
+
+`exact_dwell_lag` (bild_gauss_dwell_lag) fills the range between the filter and the smoothed marginals:
+per frame the state probabilities given the data up to `lag` frames later, for every lag up to `lag` at once.
 """
 import math
 import warnings
@@ -875,6 +878,99 @@ def exact_dwell_filter(trajs, model, prior, run_max=0, nan='propagate', scratch_
             log_predictive=predictive, log_filtered=res['log_filtered'][j, :, :T].copy(), run_length_mean=res['run_mean'][j, :T].copy(),
             log_run_length=None if res['log_run'] is None else res['log_run'][j, :, :T].copy(),
             n_nan_windows=res['n_nan_windows'][j, :T].copy()))
+    return out[0] if single else out
+
+
+# ---------------------------------------------------------------- fixed-lag smoothing under the dwell-time prior (section 26)
+
+MAX_DWELL_LAG = _lib.DWELL_LAG_MAX
+
+
+class DwellLagResults:
+    """
+    `exact_dwell_lag` of one trajectory of T frames: at frame t and lag l, what `exact_dwell` says about frame t of the
+    truncation x[:t + l + 1].
+
+    traj, model, prior, nan, lag : as given
+    log_evidence : the evidence of the whole trajectory, `exact_dwell`'s number bit for bit
+    log_lagged : (S, T, lag + 1) log P(theta_t = s | x_0 ... x_{t + l}) at [s, t, l].  Column 0 is `exact_dwell_filter`'s
+        `log_filtered`.  Where t + l + 1 >= T the data end and the entry is `exact_dwell`'s smoothed marginal: the last columns
+        of the last frames repeat, and with lag >= T - 1 column `lag` is the smoothed marginal at every frame.
+    n_nan_windows : (T,) `exact_dwell`'s `n_nan_windows` of x[:t + 1]
+
+    Under nan='propagate' entry [:, t, l] is NaN where the truncation it speaks of, x[:min(t + l + 1, T)], has
+    `n_nan_windows` > 0; a truncation without a profile of positive weight has NaN in all its entries.
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'lag', 'log_evidence', 'log_lagged', 'n_nan_windows')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return f"DwellLagResults(T={len(self.traj)}, lag={self.lag}, log_evidence={self.log_evidence!r})"
+
+    def fixed_lag(self, lag):
+        """ (S, T) log P(theta_t = s | x_0 ... x_{t + lag}): column `lag` of `log_lagged` """
+        if int(lag) != lag or not 0 <= lag <= self.lag:
+            raise ValueError(f"lag = {lag!r}: an integer in 0 ... {self.lag}")
+        return self.log_lagged[:, :, int(lag)]
+
+    def settling_lag(self, tol=1e-3):
+        """
+        (T,) int64: per frame the smallest l from which every later computed column stays within `tol` (in probability, the
+        maximum over the states) of column `lag`; `lag` where only that column does, -1 at a frame with a NaN entry.  The
+        columns l > T - 1 - t are not computed from more data: they repeat column T - 1 - t.  NumPy on the host.
+        """
+        return settling_lag(self.log_lagged, tol)
+
+
+def settling_lag(log_lagged, tol=1e-3):
+    """ `DwellLagResults.settling_lag` of an (S, T, lag + 1) array """
+    log_lagged = np.asarray(log_lagged, dtype=np.float64)
+    S, T, n = log_lagged.shape
+    p = np.exp(log_lagged)
+    off = np.max(np.abs(p - p[:, :, -1:]), axis=0) > tol        # (T, lag + 1); NaN compares False
+    # the last column that is off, -1 where none is: the answer is the column behind it
+    last_off = np.where(off.any(axis=1), n - 1 - np.argmax(off[:, ::-1], axis=1), -1)
+    out = (last_off + 1).astype(np.int64)
+    out[np.isnan(p).any(axis=(0, 2))] = -1
+    return out
+
+
+def exact_dwell_lag(trajs, model, prior, lag, nan='propagate', scratch_bytes=0):
+    """
+    Exact fixed-lag smoothing for a `GenericGaussianModel` under a dwell-time prior: for every frame t the state probabilities
+    given the data up to frame t + l, for every l = 0 ... `lag` at once -- the filter of `exact_dwell_filter` at l = 0, the
+    smoothed marginals of `exact_dwell` once the data end, and the whole curve in between: what a delayed online decision
+    gains, and how much data behind a frame its smoothed answer needs.  From the forward pass of `exact_dwell`, two sums of the
+    size of the filter's on tables that are built once, and one short backward chain per truncation
+    (bild_gauss_dwell_lag).
+
+    trajs, model, prior, nan, scratch_bytes : as for `exact_dwell`; a list gives a list of results from ONE device call
+    lag : the largest lag, an integer in 0 ... 63 (a window of lag + 1 frames is one wavefront); S x T x (lag + 1) doubles a
+        trajectory
+
+    Every refusal of `exact_dwell`, and a `lag` that is no integer, negative or above 63, is raised before the trajectories are
+    uploaded.  Returns `DwellLagResults` or a list of them.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    if isinstance(lag, (bool, np.bool_)) or int(lag) != lag or lag < 0:
+        raise ValueError(f"lag = {lag!r}: an integer >= 0")
+    if lag > MAX_DWELL_LAG:
+        raise ValueError(f"lag = {lag}: at most {MAX_DWELL_LAG}")
+    if not items:
+        return []
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_dwell_lag(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv, int(lag),
+                               omit=nan == 'omit', scratch_bytes=scratch_bytes)
+    out = []
+    for j, t in enumerate(items):
+        T = len(t)
+        out.append(DwellLagResults(
+            traj=t, model=model, prior=prior, nan=nan, lag=int(lag), log_evidence=float(res['logev'][j]),
+            log_lagged=res['log_lagged'][j, :, :T].copy(), n_nan_windows=res['n_nan_windows'][j, :T].copy()))
     return out[0] if single else out
 
 

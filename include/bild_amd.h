@@ -1179,6 +1179,48 @@ int bild_gauss_dwell_filter(const bild_gauss_model *m, const bild_gauss_trajset 
                             const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, int run_max,
                             unsigned flags, int64_t scratch_bytes, bild_dwell_filter_out *out);
 
+/* ---------------------------------------------------------------- exact fixed-lag smoothing under a dwell-time prior ----
+ * GenericGaussianModel only, at most 4 states.  Between the filter above and the smoothed marginals of
+ * bild_gauss_dwell_evidence (same tables, same NaN flag): log P(theta_t = s | x_0 .. x_{t + l}) for every frame t and every
+ * l = 0 .. lag, what bild_gauss_dwell_evidence says about frame t of the truncated trajectory x[:u], u = min(t + l + 1, T).  With
+ * that block's alpha, head(0, s) = log_init[s], w(0, b, s) = F[s][b], head(a, s) = alpha(a, s), w(a, b, s) = W[s][a - 1][b] for
+ * a >= 1, and omega_u(a, b, s) = log_dwell[s][b - a] for b < u, log_surv[s][u - a] for b = u:
+ *   gamma_u(u, s) = 0,  beta_u(a, s) = log sum_{a < b <= u} e^(omega_u(a, b, s) + W[s][a - 1][b] + gamma_u(b, s)),
+ *   gamma_u(a, s) = log sum_s'' e^(log_jump[s][s''] + beta_u(a, s''))
+ *   J_u(t, s)     = log sum_{a <= t < b <= u} e^(head(a, s) + omega_u(a, b, s) + w(a, b, s) + gamma_u(b, s))
+ *   E(u)          = log sum_s e^J_u(u - 1, s)        (the filter's E(u))
+ * A window's table entry depends on the data inside the window alone, so the tables of the whole trajectory serve every cut u.
+ * Per trajectory of T frames:
+ *   logev          the evidence of the whole trajectory as bild_gauss_dwell_evidence gives it, bit for bit: the same kernel
+ *   log_lagged     S x T_max x (lag + 1): entry [s][t][l] = J_u(t, s) - E(u).  Column 0 is the filtered marginal; where
+ *                  t + l + 1 >= T the cut is the whole trajectory and the entry is the smoothed marginal, so the last columns of
+ *                  the last frames repeat; with lag >= T - 1 column lag is the smoothed marginal at every frame.  -inf where
+ *                  the probability is 0
+ *   n_nan_windows  T_max: what bild_gauss_dwell_evidence reports as n_nan_windows of x[:t + 1], as bild_gauss_dwell_filter
+ *                  gives it; 0 behind T
+ * log_lagged behind a trajectory's T is NaN.  A NaN window enters no sum.  flags = 0 (BILD_DWELL_NAN_PROPAGATE): entry
+ * [.][t][l] is NaN exactly where n_nan_windows[u - 1] > 0 for its cut u; logev follows bild_gauss_dwell_evidence.
+ * BILD_DWELL_NAN_OMIT: the skipped windows weigh 0.  A cut without a profile of positive weight (E(u) = -inf) has NaN in all its
+ * entries.  The starts a of every sum are split at the left edge of the window: the starts a <= b - 1 - lag of an end frame b
+ * are summed once for all cuts, by eight waves (wave q: a = 1 + q, 9 + q, .. ascending, wave 0 the first segment before them)
+ * merged in wave order; the starts inside the window ascending, and the ends b of a cut by butterflies over one wavefront.  No
+ * atomics, fixed summation orders that depend on the trajectory and on lag alone, so results are bit-identical across calls,
+ * the order of the set, a trajectory alone or in a batch and scratch_bytes (chunks of whole trajectories; 0: at most 1 GiB and
+ * a third of the free device memory); a different lag moves the split, and a column then agrees with the same column under
+ * another lag to rounding only.  The terms number O(S T^2) + O(S T lag^2).  Refused before any device work: what
+ * bild_gauss_dwell_evidence refuses, lag < 0 (BILD_ERR_INVALID) and lag > BILD_DWELL_LAG_MAX = 63 (BILD_ERR_UNSUPPORTED: a window
+ * of lag + 1 frames is one wavefront).  Plain launches on the set's stream.  Synchronous. */
+#define BILD_DWELL_LAG_MAX 63
+typedef struct bild_dwell_lag_out {
+    double *logev;                          /* n_traj: bild_gauss_dwell_evidence's number, bit for bit */
+    double *log_lagged;                     /* n_traj x S x T_max x (lag + 1) */
+    int64_t *n_nan_windows;                 /* n_traj x T_max */
+} bild_dwell_lag_out;                       /* every pointer may be NULL: not written */
+
+int bild_gauss_dwell_lag(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
+                         const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, int lag,
+                         unsigned flags, int64_t scratch_bytes, bild_dwell_lag_out *out);
+
 #ifdef __cplusplus
 }
 #endif

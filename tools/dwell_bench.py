@@ -2,15 +2,17 @@
 Wall time of the exact inference under a dwell-time prior (bild_amd.exact_dwell) on the data of
 tools/segdp_bench.py (GenericGaussianModel, T = 1000 frames, S = 2, d = 3): one trajectory and a batch of 256, with the
 marginals and the expected counts, the online filter `exact_dwell_filter` (without run lengths, and on
-the single trajectory with all of them) and `exact_sample(k_max=20, marginals=True)` on the same data in the same session,
+the single trajectory with all of them), the fixed-lag smoother `exact_dwell_lag` at every `--lags`
+and `exact_sample(k_max=20, marginals=True)` on the same data in the same session,
 and one `fit_markov_prior` on 64 simulated trajectories of T = 200 (the data set of tests/test_gpu_dwell.py) with its number
 of device calls and the share of the one table build.  Each configuration runs once untimed (tables built, code loaded),
 then `--reps` times; the best wall time of a synchronous call is reported.  One JSON line per configuration.
 
-    python tools/dwell_bench.py [--T 1000] [--kmax 20] [--batch 256] [--reps 5] [--single-only] [--out FILE]
+    python tools/dwell_bench.py [--T 1000] [--kmax 20] [--batch 256] [--reps 5] [--lags 15 63] [--single-only] [--dwell-only]
+                                [--out FILE]
 
-`--single-only` runs the single-trajectory `exact_dwell` and `exact_dwell_filter` alone: the part a `rocprofv3 --kernel-trace
---stats` run is made of.
+`--single-only` runs the single-trajectory `exact_dwell`, `exact_dwell_filter` and `exact_dwell_lag` alone: the part a
+`rocprofv3 --kernel-trace --stats` run is made of.  `--dwell-only` leaves out `exact_sample` and the fit.
 """
 import argparse
 import json
@@ -58,7 +60,9 @@ def main():
     ap.add_argument('--kmax', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--lags', type=int, nargs='*', default=[15, 63])
     ap.add_argument('--single-only', action='store_true')
+    ap.add_argument('--dwell-only', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     rng = np.random.default_rng(0)
@@ -92,12 +96,21 @@ def main():
                     'trajectories_per_s': n / best, 'table_build_seconds': build, 'log_evidence': first.log_evidence,
                     'prefix_log_evidence_last': float(first.prefix_log_evidence[-1]),
                     'run_length_mean_last': float(first.run_length_mean[-1])})
+        for lag in a.lags:
+            best, res = best_of(lambda: bild_amd.exact_dwell_lag(arg, model, prior, lag), a.reps)
+            first = res if n == 1 else res[0]
+            settle = first.settling_lag()
+            report({'what': 'exact_dwell_lag', 'n_traj': n, 'T': T, 'S': 2, 'd': 3, 'lag': lag, 'seconds': best,
+                    'trajectories_per_s': n / best, 'table_build_seconds': build, 'log_evidence': first.log_evidence,
+                    'settling_lag_median': float(np.median(settle)), 'frames_not_settled': int(np.sum(settle == lag))})
         if a.single_only:
             break
+        if a.dwell_only:
+            continue
         best, res = best_of(lambda: bild_amd.exact_sample(arg, model, k_max=a.kmax, marginals=True), a.reps)
         report({'what': 'exact_sample', 'n_traj': n, 'T': T, 'S': 2, 'd': 3, 'k_max': a.kmax, 'marginals': True, 'seconds': best,
                 'trajectories_per_s': n / best})
-    if not a.single_only:
+    if not a.single_only and not a.dwell_only:
         fmodel, P_true, init_true, ftrajs = fit_data()
         t0 = time.perf_counter()
         fmodel.trajset(ftrajs)
