@@ -216,7 +216,11 @@ class ExactSamplingResults:
         return self.map_profile(self.best_k(dE))
 
     def log_marginal_posterior_k(self, k):
-        """ (S, T) log posterior state marginals of the profiles of k switches """
+        """
+        (S, T) log posterior state marginals of the profiles of k switches.  The device sums them in linear scale against
+        the level's `map_logL`: values above -600 carry all their digits, those between -600 and -700 lose them towards
+        -700, and a marginal below about -700 may be reported as -inf ("Range").
+        """
         if self._log_post is None:
             raise ValueError("the marginals were not computed: call exact_sample with marginals=True")
         return self._log_post[k]
@@ -305,6 +309,8 @@ def exact_sample(trajs, model, dE=0, k_max=20, marginals=True, nan='propagate', 
 
     MAP ties (every switch frame inside a gap gives the same log-likelihood) are broken on the trajectory's own tables: the
     smallest final state, then from the last switch backwards the smallest switch frame and the smallest preceding state.
+    The log marginals are exact down to about -600; a state marginal below about e^-700 at a frame underflows and is
+    reported as -inf, not as its finite value (`ExactSamplingResults.log_marginal_posterior_k`).
     Every refusal is raised before the trajectories are uploaded.  Returns `ExactSamplingResults` or a list of them.
     """
     single, items, transitions = _check_exact_sample(trajs, model, k_max, nan)

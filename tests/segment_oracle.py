@@ -171,3 +171,165 @@ def solve(W, F, transitions, k_max, nan='propagate', with_marginals=True):
             with np.errstate(divide='ignore'):
                 out['log_post'][k] = post - logsumexp(post, axis=0)
     return out
+
+
+# --------------------------------------------------------------------------------------------------------- fast twin
+# The same definitions, vectorised over the switch frame c and the end frame b of a level.  `solve` above is the statement;
+# tests/test_segment_wide.py holds `solve_fast` to it on every output.  The sums run in another order than the loops', so the
+# two agree to rounding, not bit for bit; the counts are exact (object arrays of Python integers) and the pointers follow the
+# loops' tie rule.  `dtype=np.longdouble` runs every sum in extended precision: the oracle's own noise is the difference.
+
+def _lse_over(x, axis):
+    """ log sum exp over `axis` in the array's own precision; -inf where every term is """
+    m = np.max(x, axis=axis, keepdims=True)
+    m = np.where(m > -np.inf, m, 0)
+    with np.errstate(divide='ignore', under='ignore'):
+        return np.squeeze(np.log(np.sum(np.exp(x - m), axis=axis, keepdims=True)) + m, axis=axis)
+
+
+def forward_fast(W, F, transitions, k_max):
+    """
+    `forward` as arrays indexed [j, b, s]: A, V, R in the dtype of W, ok / bad as object arrays of Python integers, and the
+    pointer (ptr_c, ptr_q), ptr_c = -1 where `forward` has None
+    """
+    S, T = F.shape[0], F.shape[1] - 1
+    K = k_max + 1
+    A = np.full((K, T + 1, S), -np.inf, dtype=W.dtype)
+    V = np.full((K, T + 1, S), -np.inf, dtype=W.dtype)
+    R = np.zeros((K, T + 1, S), dtype=W.dtype)
+    ok = np.zeros((K, T + 1, S), dtype=object)
+    bad = np.zeros((K, T + 1, S), dtype=object)
+    ptr_c = np.full((K, T + 1, S), -1, dtype=np.int64)
+    ptr_q = np.full((K, T + 1, S), -1, dtype=np.int64)
+    nanF = np.isnan(F[:, 1:]).T                     # (b - 1, s)
+    A[0, 1:] = V[0, 1:] = np.where(nanF, -np.inf, F[:, 1:].T)
+    R[0, 1:] = np.where(nanF | (F[:, 1:].T == -np.inf), 0.0, F[:, 1:].T)
+    ok[0, 1:] = (~nanF).astype(int).astype(object)
+    bad[0, 1:] = nanF.astype(int).astype(object)
+    ptr_c[0, 1:] = np.where(nanF, -1, 0)
+    cs, bs = np.arange(1, T), np.arange(T + 1)
+    for j in range(1, min(K, T)):       # (level j needs j + 1 <= T)
+        valid = (cs[:, None] >= j) & (cs[:, None] < bs[None, :])        # (c, b)
+        for s in range(S):
+            preds = np.nonzero(transitions[:, s])[0]
+            if not len(preds):
+                continue
+            P = len(preds)
+            w = W[s, :T - 1, :]                      # row c - 1 for c = 1 ... T - 1
+            nanw = valid & np.isnan(w)
+            good = valid & ~nanw
+            ok_p, bad_p = ok[j - 1, 1:T][:, preds], bad[j - 1, 1:T][:, preds]      # (c, p)
+            okq, badq = ok_p.sum(axis=1), bad_p.sum(axis=1)
+            ok[j, :, s] = np.dot(okq, good.astype(int).astype(object))
+            bad[j, :, s] = np.dot(badq, valid.astype(int).astype(object)) + np.dot(okq, nanw.astype(int).astype(object))
+            w3 = np.where(good, w, -np.inf)[:, None, :]                             # (c, 1, b)
+            # the maximum: the first in ascending c, then ascending s', among the predecessors that hold a profile
+            cand = (good[:, None, :] & (ok_p > 0).astype(bool)[:, :, None]).reshape((T - 1) * P, T + 1)
+            tv = np.where(cand, (V[j - 1, 1:T][:, preds][:, :, None] + w3).reshape((T - 1) * P, T + 1), -np.inf)
+            top = np.max(tv, axis=0)
+            at = np.where(top > -np.inf, np.argmax(tv, axis=0), np.argmax(cand, axis=0))
+            some = cand.any(axis=0)
+            V[j, :, s] = np.where(some, top, -np.inf)
+            ptr_c[j, :, s] = np.where(some, cs[at // P], -1)
+            ptr_q[j, :, s] = np.where(some, preds[at % P], -1)
+            terms = A[j - 1, 1:T][:, preds][:, :, None] + w3                        # (c, p, b)
+            A[j, :, s] = _lse_over(terms, (0, 1))
+            live = terms > -np.inf
+            with np.errstate(invalid='ignore', under='ignore'):
+                p = np.where(live, np.exp(terms - np.where(A[j, :, s] > -np.inf, A[j, :, s], 0)), 0.0)
+                rs = np.where(live, R[j - 1, 1:T][:, preds][:, :, None] + w3, 0.0)
+            R[j, :, s] = np.sum(p * rs, axis=(0, 1))
+    return A, V, R, ok, bad, ptr_c, ptr_q
+
+
+def backward_fast(W, transitions, k_max):
+    """ `backward` in the dtype of W """
+    S, T = W.shape[0], W.shape[1]
+    K = k_max + 1
+    G = np.full((K, T + 1, S), -np.inf, dtype=W.dtype)
+    G[0, T, :] = 0.0
+    later = np.arange(T + 1)[None, :] > np.arange(1, T)[:, None]           # (b, e): e > b
+    for m in range(1, K):
+        if T < 2:
+            break
+        for s in range(S):
+            succ = np.nonzero(transitions[s])[0]
+            if not len(succ):
+                continue
+            w = W[succ][:, :T - 1, :]               # (q, b - 1, e)
+            terms = np.where(later[None] & ~np.isnan(w), w + G[m - 1][:, succ].T[:, None, :], -np.inf)
+            G[m, 1:T, s] = _lse_over(terms, (0, 2))
+    return G
+
+
+def marginals_fast(W, F, transitions, A, G, k):
+    """ `marginals` in the dtype of W """
+    S, T = F.shape[0], F.shape[1] - 1
+    post = np.full((S, T), -np.inf, dtype=W.dtype)
+    a_, b_ = np.arange(1, T), np.arange(T + 1)
+    for s in range(S):
+        logQ = np.full((T, T + 1), -np.inf, dtype=W.dtype)
+        logQ[0, 1:] = np.where(np.isnan(F[s, 1:]), -np.inf, F[s, 1:] + G[k, 1:, s])
+        preds = np.nonzero(transitions[:, s])[0]
+        if k >= 1 and T >= 2 and len(preds):
+            w = W[s, :T - 1, :]
+            a_in = _lse_over(A[:k, 1:T][:, :, preds], 2)         # [j - 1, a]: over the states before
+            g_out = G[k - 1::-1, :, s]                          # [j - 1, b] = G[k - j, b, s]
+            both = _lse_over(a_in[:, :, None] + g_out[:, None, :], 0)
+            logQ[1:] = np.where((a_[:, None] < b_[None, :]) & ~np.isnan(w), both + w, -np.inf)
+        # post[t] = log sum over a <= t < b: the tail sums over b by a running logaddexp, then the column over a
+        tail = np.logaddexp.accumulate(logQ[:, ::-1], axis=1)[:, ::-1][:, 1:]       # [a, t] = lse over b > t
+        post[s] = _lse_over(np.where(np.arange(T)[:, None] <= np.arange(T)[None, :], tail, -np.inf), 0)
+    return post
+
+
+def solve_fast(W, F, transitions, k_max, nan='propagate', with_marginals=True, dtype=np.float64, kept=None):
+    """ `solve` by the vectorised recursions: the same dictionary, its arrays in `dtype`; a dict `kept` receives the tables """
+    transitions = np.asarray(transitions, dtype=bool)
+    W, F = np.asarray(W, dtype=dtype), np.asarray(F, dtype=dtype)
+    S, T = F.shape[0], F.shape[1] - 1
+    K = k_max + 1
+    A, V, R, ok, bad, ptr_c, ptr_q = forward_fast(W, F, transitions, k_max)
+    G = backward_fast(W, transitions, k_max) if with_marginals else None
+    if kept is not None:
+        kept.update(A=A, V=V, R=R, ok=ok, bad=bad, ptr_c=ptr_c, ptr_q=ptr_q, G=G)
+    cfc = CFC(transitions)
+    out = {'logev': np.full(K, -np.inf, dtype=dtype), 'KL': np.full(K, np.nan, dtype=dtype), 'map_logL': np.full(K, np.nan, dtype=dtype),
+           'map_states': [None] * K, 'n_profiles': [0] * K, 'n_omitted': [0] * K, 'log_post': np.full((K, S, T), np.nan, dtype=dtype)}
+    for k in range(K):
+        n_all = math.comb(T - 1, k) * int(cfc.N_total(k)) if k <= T - 1 else 0
+        n_ok, n_bad = int(sum(ok[k, T])), int(sum(bad[k, T]))
+        assert n_ok + n_bad == n_all
+        if n_all == 0:
+            continue
+        cand = [s for s in range(S) if ptr_c[k, T, s] >= 0]
+        if cand:
+            s = max(cand, key=lambda q: (V[k, T, q], -q))
+            out['map_logL'][k] = V[k, T, s]
+            states = np.empty(T, dtype=int)
+            b = T
+            for j in range(k, -1, -1):
+                c, q = int(ptr_c[j, b, s]), int(ptr_q[j, b, s])
+                states[c:b] = s
+                b, s = c, q
+            out['map_states'][k] = states
+        if nan == 'propagate':
+            out['n_profiles'][k] = n_all
+            if n_bad:
+                out['logev'][k] = np.nan
+                continue
+            count = n_all
+        else:
+            out['n_profiles'][k], out['n_omitted'][k] = n_ok, n_bad
+            count = n_ok
+        tot = _lse_over(A[k, T], 0)
+        if count == 0 or tot == -np.inf:
+            continue
+        out['logev'][k] = tot - np.log(dtype(count))
+        p = np.exp(A[k, T] - tot)
+        out['KL'][k] = np.sum(np.where(p > 0, p * R[k, T], 0.0)) - out['logev'][k]
+        if with_marginals:
+            post = marginals_fast(W, F, transitions, A, G, k)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                out['log_post'][k] = post - _lse_over(post, 0)
+    return out

@@ -50,27 +50,37 @@ def oracle_replay(model, x, uniforms, ks):
     return DO.draws(W, F, G, model.transitions, ks, uniforms)
 
 
-@pytest.mark.parametrize('name', REPLAY_CASES)
-def test_replay_against_oracle(name):
-    model, x, u, ks = replay_case(name)
-    want_start, want_state, fragile, consumed = oracle_replay(model, x, u, ks)
-    # the excused share: a condition on the inputs (expectation 2 DELTA T per uniform: under 0.1 draws per case)
-    assert fragile.sum() <= 0.001 * N_REPLAY
-    assert np.all(want_start[:, 0] == 0)        # every k = 0 ... 5 has profiles of positive weight on these cases
-    r = bild_amd.exact_sample(x, model, k_max=K_MAX, nan='omit', marginals=False)
-    d = r.draw(N_REPLAY, k=ks, uniforms=u)
+def check_replay(label, d, x, model, ks, want_start, want_state, fragile, consumed, allowed):
+    """
+    The replay assertions (shared with tests/test_gpu_segment_wide.py): `ExactDraws` d of uniforms and ks against the oracle's
+    replay of them; `allowed` is the number of fragile draws excused, a condition on the inputs
+    """
+    n = len(ks)
+    assert fragile.sum() <= allowed
+    assert np.all(want_start[:, 0] == 0)        # every k asked for has profiles of positive weight
     firm = ~fragile
     assert np.array_equal(d.seg_start[firm], want_start[firm]) and np.array_equal(d.seg_state[firm], want_state[firm])
     assert np.array_equal(d.k, ks) and d.n_switches is d.k
     assert np.array_equal(d.uniforms, consumed)
     logL = model.logL_segments(d.seg_start, d.seg_state, x)
-    print(f"{name}: fragile {int(fragile.sum())}, max |logL - logL_segments| = {np.max(np.abs(d.logL - logL)):.3e}")
+    print(f"{label}: fragile {int(fragile.sum())}, max |logL - logL_segments| = {np.max(np.abs(d.logL - logL)):.3e}")
     assert not np.any(np.isnan(d.logL))
     assert np.max(np.abs(d.logL - logL)) < 1e-10
     states = d.states()
-    assert states.shape == (N_REPLAY, len(x)) and np.array_equal(np.count_nonzero(np.diff(states, axis=1), axis=1), ks)
+    assert states.shape == (n, len(x)) and np.array_equal(np.count_nonzero(np.diff(states, axis=1), axis=1), ks)
     profiles = d.profiles()
-    assert len(profiles) == N_REPLAY and np.array_equal(np.asarray(profiles[7][:]), states[7])
+    assert len(profiles) == n and np.array_equal(np.asarray(profiles[7][:]), states[7])
+    return states
+
+
+@pytest.mark.parametrize('name', REPLAY_CASES)
+def test_replay_against_oracle(name):
+    model, x, u, ks = replay_case(name)
+    want_start, want_state, fragile, consumed = oracle_replay(model, x, u, ks)
+    r = bild_amd.exact_sample(x, model, k_max=K_MAX, nan='omit', marginals=False)
+    d = r.draw(N_REPLAY, k=ks, uniforms=u)
+    # the excused share: a condition on the inputs (expectation 2 DELTA T per uniform: under 0.1 draws per case)
+    check_replay(name, d, x, model, ks, want_start, want_state, fragile, consumed, 0.001 * N_REPLAY)
 
 
 def same_draws(a, b):
