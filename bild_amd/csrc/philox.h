@@ -1,5 +1,8 @@
-// Counter-based Philox-4x32-10 (Salmon et al., SC'11), shared by the device-side draws: the AMIS samples
-// (amis_device.hip) and the simulated trajectories (sim.hip).  Device code only.
+// Counter-based Philox-4x32-10 (Salmon et al., SC'11), shared by the five device-side draws: the AMIS samples
+// (amis_device.hip: draw_kernel), the Rouse trajectories (sim.hip), the GenericGaussianModel trajectories (gauss.hip:
+// gauss_sim_normals_kernel), the exact profile draws (gauss_segdraw.hip) and the dwell-time profile draws
+// (gauss_dwelldraw.hip).  Their counter layouts are part of the C ABI's contract (include/bild_amd.h) and are held to a
+// host statement of this file, tests/philox_oracle.py, by tests/test_gpu_device_streams.py.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -471,8 +471,12 @@ int bild_amis_step(bild_amis *m, int64_t N, const double *ss, const int64_t *the
 int bild_amis_step_fused(bild_amis *m, const bild_model *model, const bild_trajset *ts, int64_t N,
                          const double *ss, const int64_t *thetas, unsigned flags, double *evidence);
 /* The same with the N samples DRAWN on the device from the current proposal -- a counter-based generator (Philox-4x32-10)
- * keyed by `seed`, one stream per (step, sample); gamma variates by Marsaglia-Tsang, traces slot by slot from the CFC
- * weights.  Opt-in: not the reference's NumPy random stream (bild/amis.py:831-832), the same sampler in distribution.
+ * keyed by `seed`, one stream per (k + 1, index of the sample in the pool): counter (pool index low, pool index high, k + 1,
+ * block), the pool index of sample r of the step being the pool size before the step + r, so a sample is a pure function of
+ * (seed, k + 1, pool index, the proposal); uniforms two per block, words (2, 3) before words (0, 1); gamma variates by
+ * Marsaglia-Tsang, each normal the cosine of a Box-Muller pair of two uniforms, traces slot by slot from the CFC weights
+ * (tests/philox_oracle.py: amis_draw states the whole draw).  Opt-in: not the reference's NumPy random stream
+ * (bild/amis.py:831-832), the same sampler in distribution.
  * Nothing goes up but the proposal's parameters.  bild_amis_pool_samples brings the pooled samples to the host. */
 int bild_amis_step_device_rng(bild_amis *m, const bild_model *model, const bild_trajset *ts, int64_t N,
                               uint64_t seed, unsigned flags, double *evidence);

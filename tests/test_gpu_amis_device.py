@@ -205,7 +205,8 @@ def test_fused_step_equals_likelihood_call_plus_bookkeeping(built_lib):
 def test_device_rng_is_the_same_sampler_in_distribution(built_lib):
     """
     FixedkSampler(rng='device'): the samples of a step are drawn on the GPU (Philox-4x32-10, Marsaglia-Tsang gammas, traces
-    slot by slot).  Not the reference's random numbers, so nothing can be compared sample by sample; the sampler must be the
+    slot by slot).  Not the reference's random numbers, so nothing can be compared with the reference sample by sample (the
+    draws are held to a host Philox sample by sample in tests/test_gpu_device_streams.py); the sampler must be the
     same in distribution: (i) moments of the very first batch (uniform Dirichlet, uniform traces) against their exact
     values, (ii) the evidence after 6 steps against the NumPy-stream run on the same trajectory, over 20 seeds, within
     the two runs' own standard errors, (iii) reproducible for a seed, different for another one.
