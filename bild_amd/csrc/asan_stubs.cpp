@@ -40,6 +40,7 @@ int launch_kalman(const KalParams &, int, void *) { return 1; }
 int launch_kalman_mix(const MixParams &, void *) { return 1; }
 int launch_sens(const SensParams &, int, int, void *) { return 1; }
 int launch_tail(const TrajDesc *, int, int, int, int, int, const double *, const double *, const int64_t *, int64_t, double *, double *, void *) { return 1; }
+int launch_switch_tail(const TrajDesc *, int, int, int, int, int, const double *, const double *, int, const double *, const double *, const TransEntry *, const int64_t *, int64_t, int, double *, double *, void *) { return 1; }
 int launch_mark_refused_rows(const int32_t *, int, int64_t, double *, void *) { return 1; }
 int amis_dev_pass_a_rows(int64_t, int64_t) { return 0; }
 int amis_dev_draw(int, int, int64_t, uint64_t, uint64_t, const double *, const double *, const uint8_t *, double *, uint8_t *, void *) { return 1; }

@@ -165,6 +165,11 @@ struct KParams {
     const double *tail_g;
     double tail_tol;     // a mean column may be this far (relative) from the table's when the tail is taken
     int32_t tail_margin; // frames beyond the table's own transient before the next switch may come
+    // switch tails (tail.hip): per (trajectory, chain, s -> sn != s, switch frame t2) -- the entries of the transient state table,
+    // TrajDesc::strans0 -- stail_J vectors of kDMax x NP doubles: entry j is what a deviation of the means from the record of
+    // (s, t2 - j - 1) does to the log-likelihood of all later frames when the path switches to sn at t2; null: no such tails
+    const double *stail;
+    int32_t stail_J;
     // work lists (walk.hip): this launch runs only the tasks the table walk could not finish -- kWorkBuckets lists of
     // `work_cap` task indices (index into `out`) each, heaviest bucket last, with their lengths in work_counts
     const int32_t *work;
@@ -230,6 +235,12 @@ struct OneHand {
 };
 int launch_tail(const TrajDesc *d_trajs, int n_traj, int S, int NP, int d, int dstar_max, const double *d_states, const double *d_prefix,
                 const int64_t *d_first, int64_t total, double *d_gain, double *d_tail_g, void *stream);
+// switch tails: transients of more than kSwitchTailMaxM frames have no entry (the builder keeps a transient's gains in LDS)
+constexpr int kSwitchTailMaxM = 128;
+// d_stail: (S - 1) x prefix_records x J x kDMax x NP doubles, zeroed by the caller; d_gain as for launch_tail (filled again here)
+int launch_switch_tail(const TrajDesc *d_trajs, int n_traj, int S, int NP, int d, int dstar_max, const double *d_states, const double *d_tab,
+                       int tab_factored, const double *d_prefix, const double *d_tail_g, const TransEntry *d_trans, const int64_t *d_first,
+                       int64_t total, int J, double *d_gain, double *d_stail, void *stream);
 int launch_mark_refused_rows(const int32_t *seg_start, int K1, int64_t n, double *out, void *stream);
 
 // launch geometry for a padded chain length

@@ -168,6 +168,11 @@ int launch_batch(const bild_model &m, const bild_trajset &ts, int64_t n, int K1,
                     p.trans = ts.d_trans;
                     p.m_typ = ts.trans_m_typ;
                     if (ts.trans2_state == 0) ensure_pairs(m, ts, st);
+                    if (ts.stail_state == 0) ensure_switch_tails(m, ts, st);
+                    if (ts.stail_state == 1 && p.tail_g != nullptr && !(flags & BILD_NO_SWITCH_TAIL)) {
+                        p.stail = ts.d_stail;
+                        p.stail_J = ts.stail_J;
+                    }
                     if (ts.trans2_state == 1) {
                         p.trans2 = ts.d_trans2;
                         p.gap_max = ts.gap_max;

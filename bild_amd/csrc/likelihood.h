@@ -194,6 +194,12 @@ struct bild_trajset {
     mutable double *d_pstrans = nullptr;  // pair state table (common.h), filled by the launch that builds the pair table
     mutable int64_t pstrans_records = 0;  // records of the pair state table as built: prefix_records (S - 1)^2 (gap_max - 1) pnq
     mutable int pgap = 0, pstride = kPairStateStride, pnq = 0; // gaps 1 .. pgap - 1 behind the second switch, every pstride-th
+    // switch tails (tail.hip; KParams::stail), built behind the pair table: 0 not tried, 1 built, -1 none
+    mutable std::atomic<int> stail_state{0};
+    mutable double *d_stail = nullptr;
+    mutable int stail_J = 0;
+    mutable int64_t stail_bytes = 0;
+    mutable double stail_build_ms = 0.0;
     mutable int trans_m_max = 0;          // longest converged transient of the single table
     mutable int two_switch_covered = 0;  // every candidate of <= 2 switches comes out of the tables (checked on the device when the pair table is built)
     mutable int trans_m_typ = 48;         // typical frames-to-convergence of the table's entries (90th percentile): the scheduler's yardstick
@@ -217,6 +223,7 @@ size_t lds_bytes(const bild_model &m, const Geometry &geom, int mode);
 int ensure_prefix(const bild_model &m, const bild_trajset &ts, hipStream_t st);
 int ensure_transients(const bild_model &m, const bild_trajset &ts, hipStream_t st);
 int ensure_pairs(const bild_model &m, const bild_trajset &ts, hipStream_t st);
+int ensure_switch_tails(const bild_model &m, const bild_trajset &ts, hipStream_t st);
 
 // ---- launch.cpp ----------------------------------------------------------------------
 // What a launch may be given beyond the segment lists (all device-visible, all optional)

@@ -694,9 +694,13 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
         // the switch the current segment began with -- its frame, and the state in front of it (first-order tail) -- lives in the
         // task's second LDS constant: two registers live across the frame loop cost the geometries that are short of them
         // another round of spills (the pair table's builder, (2, 7): 420 -> 700 us when they were registers)
+        // (the word's upper half, bits 16 and up of the hi word: the switch the task's current chain began with -- begin_chain, read
+        // by the switch tail of a look; a switch inside the chain carries it on, one LDS read at an event, nothing in a frame)
         auto note_switch = [&](int s_from, int t_seg) {
             row_const[1] = __hiloint2double(s_from, t_seg);
         };
+        constexpr int kNoteState = 0xffff;
+        static_assert(kSegLds < (1 << 14), "a switch index fits the upper half of the noted word");
         note_switch(s, 0);
         // frame t is the first of a new segment: state bookkeeping, and the basis change of a real switch
         auto enter_segment = [&](int t) {
@@ -721,7 +725,9 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                         }
                         clk.event_ends(TaskClock::kBasisChange);
                     }
-                    note_switch(s, t);
+                    int carried = 0;
+                    if constexpr (JUMP && !BUILD) carried = __double2hiint(row_const[1]) & ~kNoteState;
+                    note_switch(s | carried, t);
                     s = sn;
                     load_state(s);
                     s_loaded = s;
@@ -904,6 +910,8 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
         // (the walk plan, below: the task's table entries are in LDS, lane by lane)
         const bool planned = use_transients && p.walk_lds != 0 && seg_in_lds;
         auto begin_chain = [&](int t_ptr) {
+            // the chain's first switch is the one into segment seg + 1, whichever record the chain physically starts from
+            const int chain0 = (JUMP && !BUILD) ? (seg + 1 <= kSegLds ? seg + 1 : kSegLds) << 16 : 0;
             if constexpr (JUMP) {
                 if (p.strans != nullptr && seg_in_lds && seg + 2 < nseg) {
                     const int sn = seg_state_of(seg + 1), t2 = seg_start_of(seg + 2), g1 = t2 - t;
@@ -933,7 +941,7 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                             }
                         }
                         seg += links; // the segment of sn (sm): the frame at t2 (t3) moves on to the next one
-                        note_switch(s_from, t_from);
+                        note_switch(s_from | chain0, t_from);
                         s = s_to;
                         next_start = t_next;
                         t = t_go;
@@ -941,6 +949,10 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                         return;
                     }
                 }
+            }
+            if constexpr (JUMP && !BUILD) {
+                const double noted = row_const[1];
+                row_const[1] = __hiloint2double((__double2hiint(noted) & kNoteState) | chain0, __double2loint(noted));
             }
             start_run(t, false, t_ptr);
         };
@@ -1248,7 +1260,9 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                     bool far = t2 >= T;
                     wave_lds_fence();
                     const double noted = row_const[1];
-                    const int t_seg = __double2loint(noted), s_from = __double2hiint(noted);
+                    const int t_seg = __double2loint(noted), s_from = __double2hiint(noted) & kNoteState;
+                    // (the vectors of the dot product: the table's own tail, or -- below -- the tail through the next switch)
+                    const double *__restrict__ g_at = p.tail_g + (td->prefix_rec0 + ((int64_t)e * S + s) * T + (t - 1)) * (kDMax * NP);
                     if (!far && p.trans != nullptr && t_seg >= 1) {
                         const int m_ref = p.trans[td->trans0 + (((int64_t)e * S + s_from) * S + s) * T + t_seg].m;
                         // ... and by what the means still have to lose: `excess` is their deviation in units of the full
@@ -1265,6 +1279,33 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                         if (!(__ballot(excess >= 0x1p12) & group_mask)) bits = 12;
                         if (!(__ballot(excess >= 0x1p8) & group_mask)) bits = 8;
                         far = m_ref > 0 && t2 - t_seg >= m_ref + kTailMargin && t2 - t >= (bits * m_ref + 29) / 30 + 4;
+                        // The switch tail (tail.hip).  The next switch is too close for the table's own tail -- whose vector is the
+                        // adjoint of the switch-free filter --, but the adjoint along the path this candidate has in front of it
+                        // (state s up to t2 - 1, the switch, the transient from a synchronised start, the new state's filter) is
+                        // in a table too, and `land` at t2 does the zeroth order.  Taken where
+                        //  (a) the table has the entry: t2 - t < J;  (b) the switch at t2 has a transient entry m1 (the lo word of
+                        //  its third plan slot, which the pair-state rewrite leaves intact);  (c) the switch behind t2 leaves that
+                        //  transient the room this look would ask of its own, so that `land` takes exactly that entry;
+                        //  (d) the look lies behind the chain's THIRD switch: a chain started from a state table skips the looks of
+                        //  its first and second gap, and the same chain run from its first switch must not end at one of them.
+                        if constexpr (!BUILD) {
+                            if (!far && m_ref > 0 && p.stail != nullptr && seg_in_lds && seg + 1 < nseg && t2 - t < p.stail_J &&
+                                seg - (__double2hiint(noted) >> 16) >= 2) {
+                                const int sn = seg_state_of(seg + 1);
+                                const int m1 = planned ? __double2loint(walk[3 * (seg + 1) + 2])
+                                                       : p.trans[td->trans0 + (((int64_t)e * S + s) * S + sn) * T + t2].m;
+                                const int n3 = (seg + 2 < nseg) ? seg_start_of(seg + 2) : INT_MAX;
+                                const int room = (n3 < T ? n3 : T) - t2;
+                                // (t2 + m1 < T: an entry of T - t2 frames is a transient that ran into the trajectory's end without
+                                // converging -- the table holds no vectors for it; only BILD_TAIL_MARGIN=0 lets one come this far)
+                                if (sn != s && m1 > 0 && m1 <= kSwitchTailMaxM && t2 + m1 < T && room >= m1 + kTailMargin &&
+                                    room >= (bits * m1 + 29) / 30 + 4) {
+                                    far = true;
+                                    const int64_t entry = td->strans0 + (((int64_t)e * S + s) * (S - 1) + (sn - (sn > s ? 1 : 0))) * T + t2;
+                                    g_at = p.stail + (entry * p.stail_J + (t2 - t)) * (kDMax * NP);
+                                }
+                            }
+                        }
                     }
                     if (far) {
                         converged = true;
@@ -1276,8 +1317,7 @@ __device__ __forceinline__ void logl_body(const KParams &p, const OneHand *hand 
                         for (int q = 0; q < CPL; ++q) {
                             mine[q] = 0.0;
                             if (isM[q]) {
-                                const double *__restrict__ gq =
-                                    p.tail_g + ((td->prefix_rec0 + ((int64_t)e * S + s) * T + (t - 1)) * kDMax + (cidx[q] - NP)) * NP;
+                                const double *__restrict__ gq = g_at + (cidx[q] - NP) * NP;
                                 double acc = 0.0;
 #pragma unroll
                                 for (int i = 0; i < NP; ++i) acc = fma(gq[i], col.v[q][i] - rec[cidx[q] * NP + i], acc);

@@ -454,6 +454,66 @@ int ensure_pairs(const bild_model &m, const bild_trajset &ts, hipStream_t st)
     return BILD_OK;
 }
 
+// The switch tails of a trajectory set (tail.hip): for every switch of the transient table with a converged transient, what a
+// deviation of the means in front of it does to everything behind it -- J vectors per switch, one for every frame a look that the
+// ordinary tail refuses for closeness can stand at.  Behind the pair table, from the byte budget of the state tables after both of
+// their levels, whole or not at all: which tables exist is a property of the set (and its declaration) alone.
+// (Unlike the state tables this one changes results, by ~1e-11: its state leaves 0 only when the build is over, under the mutex, so
+// that a second thread evaluating the set meanwhile waits here and then reads the same table -- never a launch without it.)
+static bool build_switch_tails(const bild_model &m, const bild_trajset &ts, hipStream_t st);
+int ensure_switch_tails(const bild_model &m, const bild_trajset &ts, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(ts.prefix_mu);
+    if (ts.stail_state != 0) return BILD_OK;
+    const bool built = build_switch_tails(m, ts, st);
+    ts.stail_state = built ? 1 : -1;
+    return BILD_OK;
+}
+
+static bool build_switch_tails(const bild_model &m, const bild_trajset &ts, hipStream_t st)
+{
+    if (ts.prefix_state != 1 || ts.trans_state != 1 || ts.d_tail_g == nullptr || m.has_G || m.S < 2) return false;
+    if (config().no_tail || config().no_switch_tail || ts.trans_m_max < 1) return false;
+    if (ts.expected_evals >= 0 && ts.expected_evals < kExpectPairs) return false;
+    const int S = m.S, NP = m.NPm[kModal];
+    if (NP > kMaxNP) return false;
+    // every look the ordinary tail refuses because the next switch is too close: fewer than (40 m_ref + 29) / 30 + 4 frames in
+    // front of it (the most `bits` can ask for), or a segment shorter than m_ref + margin (the look is >= 24 frames into it)
+    const int mm = std::min(ts.trans_m_max, kSwitchTailMaxM);
+    const int J = std::max((40 * mm + 29) / 30 + 4, mm + std::max(0, config().tail_margin));
+    const int64_t entries = ts.prefix_records * (S - 1);
+    const size_t bytes = (size_t)entries * J * kDMax * NP * sizeof(double);
+    const size_t rec_bytes = (size_t)prefix_record_doubles(NP) * sizeof(double);
+    size_t budget = (size_t)std::max<int64_t>(config().states_max_bytes, 0);
+    if (config().states_max_bytes < 0) budget = ts.expected_evals >= (int64_t)100000000 ? ((size_t)64 << 30) : ((size_t)4 << 30);
+    const size_t levels = (size_t)(ts.d_strans ? ts.strans_records : 0) * rec_bytes + (size_t)(ts.d_pstrans ? ts.pstrans_records : 0) * rec_bytes;
+    budget = budget > levels ? budget - levels : 0;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+    budget = std::min(budget, free_b / 3);
+    if (bytes == 0 || bytes > budget || entries >= ((int64_t)1 << 31)) return false;
+    std::vector<int64_t> first((size_t)ts.n_traj + 1, 0);
+    for (int j = 0; j < ts.n_traj; ++j) first[(size_t)j + 1] = first[j] + (int64_t)ts.dstar_max * S * ts.descs[j].T;
+    if (first.back() != ts.prefix_records) return false;
+    TabScratch scratch(st);
+    double *d_tab, *d_gain;
+    int64_t *d_first;
+    const bool ok = scratch.alloc(&d_tab, bytes) && scratch.alloc(&d_gain, (size_t)ts.prefix_records * (NP + 4) * sizeof(double)) &&
+                    scratch.alloc(&d_first, first.size() * sizeof(int64_t)) &&
+                    hipMemcpy(d_first, first.data(), first.size() * sizeof(int64_t), hipMemcpyHostToDevice) == hipSuccess &&
+                    scratch.run([&] {
+                        return hipMemsetAsync(d_tab, 0, bytes, st) == hipSuccess &&
+                               launch_switch_tail(ts.d_descs, ts.n_traj, S, NP, m.d, ts.dstar_max, m.d_states[kModal], m.d_tab[kModal],
+                                                  m.tab_factored ? 1 : 0, ts.d_prefix, ts.d_tail_g, ts.d_trans, d_first, first.back(), J, d_gain,
+                                                  d_tab, (void *)st) == 0;
+                    }, &ts.stail_build_ms);
+    if (!ok) return false;
+    ts.d_stail = scratch.keep(d_tab);
+    ts.stail_J = J;
+    ts.stail_bytes = (int64_t)bytes;
+    return true;
+}
+
 } // namespace bild
 
 extern "C" {
@@ -616,6 +676,7 @@ int bild_trajset_destroy(bild_trajset *ts)
     tab_free(ts->d_trans2);
     tab_free(ts->d_strans);
     tab_free(ts->d_pstrans);
+    tab_free(ts->d_stail);
     delete ts;
     return BILD_OK;
 }
@@ -629,9 +690,11 @@ int bild_prefix_info(const bild_trajset *ts, int64_t *bytes, double *build_ms)
                  (trans ? ts->trans_entries * (int64_t)sizeof(TransEntry) : 0) +
                  (pairs ? ts->trans2_entries * (int64_t)sizeof(TransEntry) : 0) +
                  (trans && ts->d_strans ? ts->strans_records * prefix_record_doubles(ts->model->NPm[kModal]) * (int64_t)sizeof(double) : 0) +
-                 (pairs && ts->d_pstrans ? ts->pstrans_records * prefix_record_doubles(ts->model->NPm[kModal]) * (int64_t)sizeof(double) : 0);
+                 (pairs && ts->d_pstrans ? ts->pstrans_records * prefix_record_doubles(ts->model->NPm[kModal]) * (int64_t)sizeof(double) : 0) +
+                 (ts->stail_state == 1 ? ts->stail_bytes : 0);
     if (build_ms)
-        *build_ms = (built ? ts->prefix_build_ms : 0.0) + (trans ? ts->trans_build_ms : 0.0) + (pairs ? ts->trans2_build_ms : 0.0);
+        *build_ms = (built ? ts->prefix_build_ms : 0.0) + (trans ? ts->trans_build_ms : 0.0) + (pairs ? ts->trans2_build_ms : 0.0) +
+                    (ts->stail_state == 1 ? ts->stail_build_ms : 0.0);
     return BILD_OK;
 }
 

@@ -90,6 +90,15 @@ typedef enum bild_status {
  * results differ by ~1e-12 (second-order terms of a deviation below 2^-20).  (Environment BILD_NO_TAIL=1: never build the vectors.) */
 #define BILD_NO_TAIL 0x200u
 
+/* Do not end a chain of close switches on a first-order tail THROUGH its next switch (csrc/tail.hip, "switch tails": behind the
+ * third switch of a chain, a look that finds the covariance converged but the next switch too close for the ordinary tail takes
+ * the dot product with a vector whose adjoint runs through that switch and the transient behind it, kept in a table of
+ * T x S (S - 1) x d* x J x 240 bytes -- ~36 MB per 1000 frames of a 2-state trajectory, from the byte budget of the state tables
+ * after both of their levels, built whole or not at all).  With the flag, results are those of a set without the table, bit for
+ * bit; without it they differ by ~1e-11, the class of BILD_NO_TAIL.  (Environment BILD_NO_SWITCH_TAIL=1: never build the table.
+ * BILD_NO_TAIL, flag or environment, switches both kinds of tail off.) */
+#define BILD_NO_SWITCH_TAIL 0x400u
+
 /* bild_model_create flags */
 #define BILD_MODEL_NO_REDUCE 1u /* keep all N modes: skip the invariant-subspace reduction */
 
