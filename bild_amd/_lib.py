@@ -188,6 +188,11 @@ _SIGNATURES = {
                                                ctypes.c_int64, _vp]),
     'bild_gauss_dwell_lag': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
                                             ctypes.c_int64, _vp]),
+    # exact switch counts and first-contact times under a dwell-time prior (gauss_dwellevent.cpp)
+    'bild_gauss_dwell_switch_counts': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
+                                                      ctypes.c_int64, _vp]),
+    'bild_gauss_dwell_first_contact': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_uint, ctypes.c_uint,
+                                                      ctypes.c_int64, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1449,6 +1454,49 @@ def gauss_dwell_lengths(model, ts, log_init, log_jump, log_dwell, log_surv, omit
     spec = DwellLengthsOut(**{name: aptr(a) for name, a in res.items()})
     check(lib().bild_gauss_dwell_lengths(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
                                          DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
+    return res
+
+
+class DwellSwitchCountsOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'n_nan_windows', 'log_count', 'log_tail')]
+
+
+def gauss_dwell_switch_counts(model, ts, log_init, log_jump, log_dwell, log_surv, k_max, omit=False, scratch_bytes=0):
+    """
+    exact posterior switch counts under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_switch_counts): a
+    dict of logev, log_tail (n_traj,), n_nan_windows (n_traj,) int64 and log_count (n_traj, k_max + 1, S)
+    """
+    S = model.S
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
+    n = ts.n_traj
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_count': np.empty((n, max(int(k_max), -1) + 1, S)),
+           'log_tail': np.empty(n)}     # (a negative k_max: no column, and the call refuses it)
+    spec = DwellSwitchCountsOut(**{name: aptr(a) for name, a in res.items()})
+    check(lib().bild_gauss_dwell_switch_counts(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
+                                               int(k_max), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes),
+                                               ctypes.byref(spec)))
+    return res
+
+
+class DwellFirstContactOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'n_nan_windows', 'log_first', 'log_never')]
+
+
+def gauss_dwell_first_contact(model, ts, log_init, log_jump, log_dwell, log_surv, target, omit=False, scratch_bytes=0):
+    """
+    exact posterior first-contact times under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_first_contact),
+    target the bit mask of the states of the set: a dict of logev, log_never (n_traj,), n_nan_windows (n_traj,) int64 and
+    log_first (n_traj, T_max), NaN behind a trajectory's T; T_max the set's longest trajectory
+    """
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
+    n = ts.n_traj
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_first': np.empty((n, T_max)), 'log_never': np.empty(n)}
+    spec = DwellFirstContactOut(**{name: aptr(a) for name, a in res.items()})
+    check(lib().bild_gauss_dwell_first_contact(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
+                                               int(target), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes),
+                                               ctypes.byref(spec)))
     return res
 
 

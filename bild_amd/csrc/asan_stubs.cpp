@@ -129,6 +129,11 @@ namespace bild {
 int launch_dwell_lag_bases(const DwellParams &, const DwellLag &, void *) { return 1; }
 int launch_dwell_lag_windows(const DwellParams &, const DwellLag &, void *) { return 1; }
 }
+#include "gauss_dwellevent.h"
+namespace bild {
+int launch_dwell_level(const DwellParams &, const DwellLevels &, int, void *) { return 1; }
+int launch_dwell_contact(const DwellParams &, const DwellContact &, void *) { return 1; }
+}
 #include "gauss_dwelldraw.h"
 namespace bild {
 int launch_dwelldraw_head(const DwelldrawParams &, void *) { return 1; }

@@ -83,17 +83,21 @@ int DwellCall::open(CallFrame &call, const bild_gauss_model *m, const bild_gauss
 {
     sets = sets_;
     BILD_TRY(call.open(m, ts));
-    BILD_TRY(call.chunk_of(dwell_table_bytes(sets, S, Tm) + own_bytes, scratch_bytes, n, &chunk));
+    const bool two = prior2[0] != nullptr;
+    BILD_TRY(call.chunk_of(dwell_table_bytes(sets, S, Tm) + (two ? dwell_table_bytes(kDwellForward, S, Tm) : 0) + own_bytes,
+                           scratch_bytes, n, &chunk));
 
-    // the four prior tables in one device block (synchronous copy: `host` ends here)
-    const size_t len[4] = {(size_t)S, (size_t)S * S, (size_t)S * L, (size_t)S * L};
-    const double **member[4] = {&p.log_init, &p.log_jump, &p.log_dwell, &p.log_surv};
+    // the four prior tables, and the second block's two, in one device block (synchronous copy: `host` ends here)
+    const size_t len[6] = {(size_t)S, (size_t)S * S, (size_t)S * L, (size_t)S * L, (size_t)S, (size_t)S * S};
+    const double *from[6] = {prior[0], prior[1], prior[2], prior[3], prior2[0], prior2[1]};
+    const double **member[6] = {&p.log_init, &p.log_jump, &p.log_dwell, &p.log_surv, &p2.log_init, &p2.log_jump};
+    const int blocks = two ? 6 : 4;
     std::vector<double> host;
-    for (int t = 0; t < 4; ++t) host.insert(host.end(), prior[t], prior[t] + len[t]);
+    for (int t = 0; t < blocks; ++t) host.insert(host.end(), from[t], from[t] + len[t]);
     double *d = nullptr;
     BILD_TRY(call.alloc(&d, host.size()));
     HIP_TRY(hipMemcpy(d, host.data(), host.size() * 8, hipMemcpyHostToDevice));
-    for (int t = 0; t < 4; d += len[t++]) *member[t] = d;
+    for (int t = 0; t < blocks; d += len[t++]) *member[t] = d;
 
     const int ld = Tm + 1, ntile = dwell_ntile(Tm);
     const int64_t slot = (int64_t)S * ld;
@@ -111,6 +115,15 @@ int DwellCall::open(CallFrame &call, const bild_gauss_model *m, const bild_gauss
         fin.resize((size_t)chunk * 2);
         n_nan.resize((size_t)chunk);
     }
+    if (two) {
+        const double *init2 = p2.log_init, *jump2 = p2.log_jump;
+        p2 = p;
+        p2.log_init = init2, p2.log_jump = jump2;
+#define X(name, set, entries) \
+    if ((set) == kDwellForward) BILD_TRY(call.alloc(&p2.name, (size_t)chunk * (size_t)(entries)));
+        BILD_DWELL_TABLES(X)
+#undef X
+    }
     return BILD_OK;
 }
 
@@ -122,6 +135,11 @@ int DwellCall::run(CallFrame &call, const GaussTraj *trajs, int nc)
         return fail(BILD_ERR_HIP, "launch of the forward pass of the dwell-time recursion failed");
     if ((sets & kDwellBackward) && launch_dwell_backward(p, call.st))
         return fail(BILD_ERR_HIP, "launch of the backward pass of the dwell-time recursion failed");
+    if (prior2[0]) {
+        p2.trajs = trajs;
+        p2.n_traj = nc;
+        if (launch_dwell_forward(p2, call.st)) return fail(BILD_ERR_HIP, "launch of the forward pass on the second prior block failed");
+    }
     return BILD_OK;
 }
 

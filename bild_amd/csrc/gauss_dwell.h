@@ -107,6 +107,9 @@ DwellVerdict dwell_nan_rule(const double *fin, long long n_nan, bool omit);
 //   check()      what a call refuses before it touches the device: out, flags, dwell_check_call.  Fills n_traj, T, S, L, omit
 //                and Tm (the set's longest, at least 1).  Where n_traj is 0, a call returns BILD_OK behind it.
 //   over()       (the draws) the chunks run over n of the set's trajectories, the longest of Tm frames
+//   second()     (the first-contact times) a second prior block: another log_init and log_jump over the same log_dwell and
+//                log_surv.  open() then uploads it too and gives it forward tables of its own in p2 (a trajectory costs the
+//                forward tables twice), and run() ends with the forward pass on it.  The two arrays outlive open()
 //   open()       the frame on the set's stream, the chunks (a trajectory costs the tables of `sets` and the call's own
 //                `own_bytes`), the prior's upload, the tables and p
 //   run()        per chunk: the forward pass (kDwellForward) and the backward pass (kDwellBackward) of nc trajectories
@@ -115,20 +118,21 @@ struct DwellCall {
     int n_traj = 0, n = 0, S = 0, L = 0, Tm = 1, chunk = 0;
     const int *T = nullptr;
     bool omit = false;
-    DwellParams p{};
+    DwellParams p{}, p2{};          // p2: p with the second block's log_init, log_jump and forward tables (second() only)
     std::vector<double> fin;
     std::vector<long long> n_nan;
 
     int check(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init, const double *log_jump,
               const double *log_dwell, const double *log_surv, int T_max, unsigned flags, int64_t scratch_bytes, const void *out);
     void over(int n_used, int Tm_used) { n = n_used, Tm = Tm_used; }
+    void second(const double *log_init2, const double *log_jump2) { prior2[0] = log_init2, prior2[1] = log_jump2; }
     int open(CallFrame &call, const bild_gauss_model *m, const bild_gauss_trajset *ts, unsigned sets, int64_t own_bytes);
     int run(CallFrame &call, const GaussTraj *trajs, int nc);
     int read_back(CallFrame &call, int nc);
     DwellVerdict verdict(int i) const { return dwell_nan_rule(fin.data() + 2 * i, n_nan[i], omit); }
 
 private:
-    const double *prior[4] = {};
+    const double *prior[4] = {}, *prior2[2] = {};
     int64_t scratch_bytes = 0;
     unsigned sets = 0;
 };

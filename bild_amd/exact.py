@@ -35,6 +35,10 @@ log-likelihoods.
 
 `exact_dwell_lag` (bild_gauss_dwell_lag) fills the range between the filter and the smoothed marginals:
 per frame the state probabilities given the data up to `lag` frames later, for every lag up to `lag` at once.
+
+`exact_dwell_switch_counts` and `exact_dwell_first_contact` (bild_gauss_dwell_switch_counts, bild_gauss_dwell_first_contact;
+DESIGN.md section 27) are the exact posteriors of two functionals of the whole profile: the number of switches, and the first
+frame in a set of states together with the probability that there is none.
 """
 import math
 import warnings
@@ -1042,6 +1046,15 @@ class ExactDwellDraws:
             use &= ~last
         return (ends - starts)[use].astype(np.int64)
 
+    def first_contact(self, target):
+        """
+        (n,) int array: the first frame of each draw whose state is ``target`` or, for a collection, one of its states; -1 where
+        the draw never is (host only).  The histogram counterpart of `exact_dwell_first_contact`.
+        """
+        wanted = [target] if isinstance(target, (int, np.integer)) else list(target)
+        hit = np.isin(self._states[:, :self.T], np.asarray(wanted, dtype=np.int64))
+        return np.where(hit.any(axis=1), hit.argmax(axis=1), -1).astype(np.int64)
+
 
 def exact_dwell_draw(results, n, seed=0, uniforms=None, keep_uniforms=0, scratch_bytes=0):
     """
@@ -1351,6 +1364,167 @@ def exact_dwell_lengths(trajs, model, prior, nan='propagate', scratch_bytes=0):
                              n_nan_windows=int(res['n_nan_windows'][j]), expected_jumps=res['exp_jumps'][j].copy(),
                              expected_init=res['exp_init'][j].copy(), expected_dwell=res['exp_dwell'][j, :, :len(t)].copy(),
                              expected_censored=res['exp_cens'][j, :, :len(t)].copy())
+           for j, t in enumerate(items)]
+    return out[0] if single else out
+
+
+# ---------------------------------------------------------------- switch counts and first-contact times (section 27)
+
+class DwellSwitchCounts:
+    """
+    `exact_dwell_switch_counts` of one trajectory of T frames: the exact posterior of the number K of switches.
+
+    traj, model, prior, nan : as given
+    log_evidence, n_nan_windows : `exact_dwell`'s numbers, bit for bit
+    log_count : (k_max + 1, S) log P(K = n, theta_{T-1} = s | data) at [n, s]; -inf where the probability is 0 and for n > T - 1
+    log_tail : log P(K > k_max | data), computed as log(max(0, 1 - sum exp `log_count`)): a difference from 1, accurate to about
+        1e-15 of the probability and no better; -inf exactly when k_max >= T - 1
+
+    Under nan='propagate' a trajectory with `n_nan_windows` > 0 is NaN in all but `n_nan_windows`; a trajectory without a
+    profile of positive weight has `log_evidence` -inf and NaN elsewhere.
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'log_evidence', 'n_nan_windows', 'log_count', 'log_tail')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return (f"DwellSwitchCounts(T={len(self.traj)}, k_max={len(self.log_count) - 1}, log_evidence={self.log_evidence!r}, "
+                f"n_nan_windows={self.n_nan_windows})")
+
+    def pmf(self):
+        """ (k_max + 1,) P(K = n | data): the states summed in ascending order.  It sums to 1 - exp(`log_tail`). """
+        return np.exp(self.log_count).sum(axis=1)
+
+    def mean(self):
+        """ sum_n n P(K = n | data): the posterior mean of K when k_max is complete (k_max >= T - 1), a lower bound otherwise """
+        return float(np.arange(len(self.log_count)) @ self.pmf())
+
+    def segment_count_pmf(self, state):
+        """
+        ((k_max + 2) // 2 + 1,) the probability that `state` has j segments, at [j], among the profiles of at most k_max switches (it
+        sums to 1 - exp(`log_tail`)).  Two states only, where the states alternate: a profile of K switches that ends in q has
+        ceil((K + 1) / 2) segments in q and floor((K + 1) / 2) in the other state.  With three states or more the number of
+        segments of one state is not a function of K and the last state (it needs a recursion of its own inside every level):
+        NotImplementedError, histogram `exact_dwell_draw`'s profiles instead.
+        """
+        S = self.log_count.shape[1]
+        if S != 2:
+            raise NotImplementedError(f"segment_count_pmf is derived for two states, where the states alternate; the model has {S}: "
+                                      f"count the segments of the profiles of exact_dwell_draw instead")
+        if state not in (0, 1):
+            raise ValueError(f"state = {state!r}: 0 or 1")
+        weight = np.exp(self.log_count)
+        out = np.zeros((len(weight) + 1) // 2 + 1)
+        for n in range(len(weight)):
+            for q in range(2):
+                out[(n + 2) // 2 if q == state else (n + 1) // 2] += weight[n, q]
+        return out
+
+
+def exact_dwell_switch_counts(trajs, model, prior, k_max=None, nan='propagate', scratch_bytes=0):
+    """
+    The exact posterior distribution of the number of switches of a `GenericGaussianModel` profile under a dwell-time prior,
+    jointly with the last state: the forward recursion of `exact_dwell` resolved by the number of switches, one device
+    launch per level (bild_gauss_dwell_switch_counts).  No draws, no histogram noise in the tail.
+
+    trajs, model, prior, nan, scratch_bytes : as for `exact_dwell`; a list gives a list of results from ONE device call
+    k_max : the levels 0 ... k_max are computed; None: T - 1 of the longest trajectory, the complete distribution.  At most that.
+
+    Every refusal is `exact_dwell`'s, or a `k_max` that is negative or beyond the longest trajectory's T - 1, and is raised
+    before the trajectories are uploaded.  Returns `DwellSwitchCounts` or a list of them.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    top = max([len(t) for t in items] + [1]) - 1
+    if k_max is None:
+        k_max = top
+    if isinstance(k_max, bool) or not isinstance(k_max, (int, np.integer)) or k_max < 0 or k_max > top:
+        raise ValueError(f"k_max = {k_max!r}: an integer from 0 to {top}, the longest trajectory's T - 1, or None for that")
+    if not items:
+        return []
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_dwell_switch_counts(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv, int(k_max),
+                                         omit=nan == 'omit', scratch_bytes=scratch_bytes)
+    out = [DwellSwitchCounts(traj=t, model=model, prior=prior, nan=nan, log_evidence=float(res['logev'][j]),
+                             n_nan_windows=int(res['n_nan_windows'][j]), log_count=res['log_count'][j].copy(),
+                             log_tail=float(res['log_tail'][j]))
+           for j, t in enumerate(items)]
+    return out[0] if single else out
+
+
+class DwellFirstContact:
+    """
+    `exact_dwell_first_contact` of one trajectory of T frames: the exact posterior of the first frame in a target set of states.
+
+    traj, model, prior, nan : as given
+    target : the states of the set, a sorted tuple
+    log_evidence, n_nan_windows : `exact_dwell`'s numbers, bit for bit
+    log_first : (T,) log P(the first frame in the set is t | data); -inf where the probability is 0
+    log_never : log P(no frame is in the set | data), the censoring term of a pooled first-passage analysis
+
+    Each is normalised by `log_evidence`, not by their sum: that they add up to 1 holds to rounding.  Under nan='propagate' a
+    trajectory with `n_nan_windows` > 0 is NaN in all but `n_nan_windows`; a trajectory without a profile of positive weight
+    has `log_evidence` -inf and NaN elsewhere.
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'target', 'log_evidence', 'n_nan_windows', 'log_first', 'log_never')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return (f"DwellFirstContact(T={len(self.traj)}, target={self.target}, log_evidence={self.log_evidence!r}, "
+                f"log_never={self.log_never!r})")
+
+    def cdf(self):
+        """ (T,) P(the set has been entered by frame t | data), the running sum of exp `log_first`; 1 - cdf()[-1] is the never share """
+        return np.cumsum(np.exp(self.log_first))
+
+
+def _target_states(target, S):
+    """ `exact_dwell_first_contact`'s target as a sorted tuple of states: a non-empty proper subset of 0 ... S - 1 """
+    try:
+        states = list(target)
+    except TypeError:       # one state
+        states = [target]
+    if any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) for s in states):
+        raise ValueError(f"target = {target!r}: a state or a collection of states")
+    states = sorted(set(int(s) for s in states))
+    if not states:
+        raise ValueError("target is empty: no state to reach")
+    if states[0] < 0 or states[-1] >= S:
+        raise ValueError(f"target = {target!r}: the model's states are 0 ... {S - 1}")
+    if len(states) == S:
+        raise ValueError(f"target = {target!r} holds every state: the first frame is always in it")
+    return tuple(states)
+
+
+def exact_dwell_first_contact(trajs, model, prior, target, nan='propagate', scratch_bytes=0):
+    """
+    The exact posterior distribution of the first frame at which a `GenericGaussianModel` profile is in one of the states
+    `target` under a dwell-time prior, and the probability that it never is: a forward pass over the profiles that avoid the
+    set, combined with the backward tables of `exact_dwell` (bild_gauss_dwell_first_contact).  No
+    draws, no histogram noise in the early frames.
+
+    trajs, model, prior, nan, scratch_bytes : as for `exact_dwell`; a list gives a list of results from ONE device call
+    target : a state or a collection of states, a non-empty proper subset of the model's (so a model of one state is refused)
+
+    Every refusal is `exact_dwell`'s or the target's (ValueError) and is raised before the trajectories are uploaded.
+    Returns `DwellFirstContact` or a list of them.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    states = _target_states(target, model.msd.shape[0])
+    if not items:
+        return []
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_dwell_first_contact(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
+                                         sum(1 << s for s in states), omit=nan == 'omit', scratch_bytes=scratch_bytes)
+    out = [DwellFirstContact(traj=t, model=model, prior=prior, nan=nan, target=states, log_evidence=float(res['logev'][j]),
+                             n_nan_windows=int(res['n_nan_windows'][j]), log_first=res['log_first'][j, :len(t)].copy(),
+                             log_never=float(res['log_never'][j]))
            for j, t in enumerate(items)]
     return out[0] if single else out
 

@@ -1234,6 +1234,79 @@ int bild_gauss_dwell_lag(const bild_gauss_model *m, const bild_gauss_trajset *ts
                          const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, int lag,
                          unsigned flags, int64_t scratch_bytes, bild_dwell_lag_out *out);
 
+/* ---------------------------------------------------------------- switch counts under a dwell-time prior ----
+ * GenericGaussianModel only, at most 4 states.  The exact posterior distribution of the number K of
+ * switches of the profile, jointly with its last state, under the dwell-time prior of bild_gauss_dwell_evidence (same tables,
+ * same NaN flag): that block's forward recursion resolved by the number of switches.  For n = 0 .. k_max:
+ *   A_0(b, s)     = log_init[s] + omega_s(0, b) + F[s][b]
+ *   A_n(b, s)     = log sum_{c = n .. b - 1} exp(alpha_{n-1}(c, s) + omega_s(c, b) + W[s][c - 1][b])        (n >= 1, n < b <= T)
+ *   alpha_n(c, s) = log sum_s' exp(A_n(c, s') + log_jump[s'][s])                                         (1 <= c < T)
+ * Level n reads level n - 1 alone: one launch per level, two rows of alpha in memory, O(S T) per trajectory beside the
+ * output column.  Per trajectory of T frames:
+ *   logev, n_nan_windows   as bild_gauss_dwell_evidence gives them, bit for bit: the same forward kernel on the same tables
+ *   log_count      (k_max + 1) x S: entry [n][s] = A_n(T, s) - logev = log P(K = n, theta_{T-1} = s | x); -inf where the
+ *                  probability is 0, and -inf for n > T - 1
+ *   log_tail       log(max(0, 1 - sum_{n, s} exp(log_count[n][s]))), the sum over n ascending and s ascending inside: the
+ *                  probability of more than k_max switches.  A DIFFERENCE from 1: accurate to an absolute 1e-15 or so of the
+ *                  probability, not relatively, and 0 (-inf) or a few 1e-16 where the true tail is below that.  -inf exactly
+ *                  when k_max >= T - 1
+ * A NaN window enters no sum.  flags = 0 (BILD_DWELL_NAN_PROPAGATE): a trajectory with n_nan_windows > 0 has NaN in logev,
+ * log_count and log_tail; the other trajectories are untouched.  BILD_DWELL_NAN_OMIT: the skipped windows weigh 0.  A
+ * trajectory without a profile of positive weight has logev -inf and NaN in log_count and log_tail.  sum_n exp(log_count)
+ * is 1 at k_max >= T - 1 up to rounding only: logev is the forward pass's number, not the sum of the levels.  The switches c
+ * of a level are summed by eight waves, wave q taking c = n + q, n + q + 8, .. in ascending order, the waves merged in wave
+ * order: no atomics, fixed summation orders that depend on the trajectory alone, so results are bit-identical across calls,
+ * the order of the set, a trajectory alone or in a batch, scratch_bytes (chunks of whole trajectories; 0: at most 1 GiB and a
+ * third of the free device memory), and k_max: the levels n <= k_max of a call are those of every call with a larger k_max.
+ * Refused before any device work: what bild_gauss_dwell_evidence refuses, k_max < 0 and k_max > max(T_max, 1) - 1
+ * (BILD_ERR_INVALID).  Plain launches on the set's stream.  Synchronous. */
+typedef struct bild_dwell_switch_counts_out {
+    double *logev;                          /* n_traj */
+    int64_t *n_nan_windows;                 /* n_traj */
+    double *log_count;                      /* n_traj x (k_max + 1) x S */
+    double *log_tail;                       /* n_traj */
+} bild_dwell_switch_counts_out;             /* every pointer may be NULL: not written */
+
+int bild_gauss_dwell_switch_counts(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
+                                   const double *log_jump, const double *log_dwell, const double *log_surv, int T_max, int k_max,
+                                   unsigned flags, int64_t scratch_bytes, bild_dwell_switch_counts_out *out);
+
+/* ---------------------------------------------------------------- first-contact times under a dwell-time prior ----
+ * GenericGaussianModel only, at most 4 states.  The exact posterior distribution of the first frame at
+ * which the profile is in a state of the set G (bit s of target: state s belongs to G), and the probability that it never
+ * is, under the dwell-time prior of bild_gauss_dwell_evidence (same tables, same NaN flag).  With Ax the table A of that
+ * block's forward pass under the prior with log_init[s] = -inf and log_jump[.][s] = -inf for s in G (the profiles that avoid G;
+ * the same forward kernel on a second prior block) and beta, gamma of the full prior:
+ *   h(s)     = log sum_{b = 1 .. T} exp(omega_s(0, b) + F[s][b] + gamma(b, s))
+ *   first(0) = log sum_{s in G} exp(log_init[s] + h(s)) - logev
+ *   first(t) = log sum_{s' not in G} sum_{s in G} exp(Ax(t, s') + log_jump[s'][s] + beta(t, s)) - logev        (1 <= t < T)
+ *   never    = log sum_{s' not in G} exp(Ax(T, s')) - logev
+ * Per trajectory of T frames:
+ *   logev, n_nan_windows   as bild_gauss_dwell_evidence gives them, bit for bit: the same forward kernel on the same tables
+ *   log_first      T_max: first(t), -inf where the probability is 0; NaN behind T
+ *   log_never      never
+ * Every term is normalised by logev of the full forward pass, not by their sum: sum_t exp(log_first[t]) + exp(log_never) = 1
+ * holds up to rounding and is a check, not a construction.  A NaN window enters no sum.  flags = 0
+ * (BILD_DWELL_NAN_PROPAGATE): a trajectory with n_nan_windows > 0 (of the full pass) has NaN in logev, log_first and
+ * log_never; the other trajectories are untouched.  BILD_DWELL_NAN_OMIT: the skipped windows weigh 0.  A trajectory without a
+ * profile of positive weight has logev -inf and NaN in log_first and log_never.  h(s) is summed by one wavefront, lane l
+ * taking b = 1 + l, 65 + l, .. ascending, merged by butterflies; first(t) over s' ascending and s ascending inside: no
+ * atomics, fixed summation orders that depend on the trajectory alone, so results are bit-identical across calls, the order
+ * of the set, a trajectory alone or in a batch, and scratch_bytes (chunks of whole trajectories, which hold the forward tables
+ * twice; 0: at most 1 GiB and a third of the free device memory).  Refused before any device work: what
+ * bild_gauss_dwell_evidence refuses, and a target that is empty, names a state the model does not have or holds every state
+ * (BILD_ERR_INVALID): a model of one state is always refused.  Plain launches on the set's stream.  Synchronous. */
+typedef struct bild_dwell_first_contact_out {
+    double *logev;                          /* n_traj */
+    int64_t *n_nan_windows;                 /* n_traj */
+    double *log_first;                      /* n_traj x T_max */
+    double *log_never;                      /* n_traj */
+} bild_dwell_first_contact_out;             /* every pointer may be NULL: not written */
+
+int bild_gauss_dwell_first_contact(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
+                                   const double *log_jump, const double *log_dwell, const double *log_surv, int T_max,
+                                   unsigned target, unsigned flags, int64_t scratch_bytes, bild_dwell_first_contact_out *out);
+
 #ifdef __cplusplus
 }
 #endif
