@@ -193,6 +193,9 @@ _SIGNATURES = {
                                                       ctypes.c_int64, _vp]),
     'bild_gauss_dwell_first_contact': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_uint, ctypes.c_uint,
                                                       ctypes.c_int64, _vp]),
+    # exact posterior of the frames in a set of states under a dwell-time prior (gauss_dwellocc.cpp)
+    'bild_gauss_dwell_occupancy': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_uint, ctypes.c_uint,
+                                                  ctypes.c_int64, _vp]),
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
@@ -1497,6 +1500,28 @@ def gauss_dwell_first_contact(model, ts, log_init, log_jump, log_dwell, log_surv
     check(lib().bild_gauss_dwell_first_contact(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
                                                int(target), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes),
                                                ctypes.byref(spec)))
+    return res
+
+
+class DwellOccupancyOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'n_nan_windows', 'log_occ')]
+
+
+def gauss_dwell_occupancy(model, ts, log_init, log_jump, log_dwell, log_surv, target, omit=False, scratch_bytes=0):
+    """
+    exact posterior of the number of frames in a set of states under a dwell-time prior for every trajectory of the set
+    (bild_gauss_dwell_occupancy), target the bit mask of the states of the set: a dict of logev (n_traj,), n_nan_windows
+    (n_traj,) int64 and log_occ (n_traj, T_max + 1, S), -inf behind a trajectory's T; T_max the set's longest trajectory
+    """
+    S = model.S
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
+    n = ts.n_traj
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_occ': np.empty((n, T_max + 1, S))}
+    spec = DwellOccupancyOut(**{name: aptr(a) for name, a in res.items()})
+    check(lib().bild_gauss_dwell_occupancy(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
+                                           int(target), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes),
+                                           ctypes.byref(spec)))
     return res
 
 

@@ -134,6 +134,10 @@ namespace bild {
 int launch_dwell_level(const DwellParams &, const DwellLevels &, int, void *) { return 1; }
 int launch_dwell_contact(const DwellParams &, const DwellContact &, void *) { return 1; }
 }
+#include "gauss_dwellocc.h"
+namespace bild {
+int launch_dwell_occupancy(const DwellParams &, const DwellOccupancy &, int, void *) { return 1; }
+}
 #include "gauss_dwelldraw.h"
 namespace bild {
 int launch_dwelldraw_head(const DwelldrawParams &, void *) { return 1; }

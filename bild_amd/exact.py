@@ -39,6 +39,9 @@ per frame the state probabilities given the data up to `lag` frames later, for e
 `exact_dwell_switch_counts` and `exact_dwell_first_contact` (bild_gauss_dwell_switch_counts, bild_gauss_dwell_first_contact;
 DESIGN.md section 27) are the exact posteriors of two functionals of the whole profile: the number of switches, and the first
 frame in a set of states together with the probability that there is none.
+
+`exact_dwell_occupancy` (bild_gauss_dwell_occupancy) is the exact posterior of a third: the number of
+frames spent in a set of states, the looped fraction of the trajectory; `pooled_occupancy` is that of a whole data set.
 """
 import math
 import warnings
@@ -1055,6 +1058,14 @@ class ExactDwellDraws:
         hit = np.isin(self._states[:, :self.T], np.asarray(wanted, dtype=np.int64))
         return np.where(hit.any(axis=1), hit.argmax(axis=1), -1).astype(np.int64)
 
+    def occupancy(self, target):
+        """
+        (n,) int array: the number of frames of each draw whose state is ``target`` or, for a collection, one of its states
+        (host only).  The histogram counterpart of `exact_dwell_occupancy`.
+        """
+        wanted = [target] if isinstance(target, (int, np.integer)) else list(target)
+        return np.isin(self._states[:, :self.T], np.asarray(wanted, dtype=np.int64)).sum(axis=1).astype(np.int64)
+
 
 def exact_dwell_draw(results, n, seed=0, uniforms=None, keep_uniforms=0, scratch_bytes=0):
     """
@@ -1527,6 +1538,117 @@ def exact_dwell_first_contact(trajs, model, prior, target, nan='propagate', scra
                              log_never=float(res['log_never'][j]))
            for j, t in enumerate(items)]
     return out[0] if single else out
+
+
+# ---------------------------------------------------------------- looped time (section 28)
+
+class DwellOccupancy:
+    """
+    `exact_dwell_occupancy` of one trajectory of T frames: the exact posterior of the number N of frames in a target set of
+    states.  Every frame counts, observed or missing.
+
+    traj, model, prior, nan : as given
+    target : the states of the set, a sorted tuple
+    log_evidence, n_nan_windows : `exact_dwell`'s numbers, bit for bit
+    log_occupancy : (T + 1, S) log P(N = n, theta_{T-1} = s | data) at [n, s]; -inf where the probability is 0
+
+    Normalised by `log_evidence`, not by its sum: that it adds up to 1 holds to rounding.  Under nan='propagate' a trajectory
+    with `n_nan_windows` > 0 is NaN in all but `n_nan_windows`; a trajectory without a profile of positive weight has
+    `log_evidence` -inf and NaN elsewhere.
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'target', 'log_evidence', 'n_nan_windows', 'log_occupancy')
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+    def __repr__(self):
+        return (f"DwellOccupancy(T={len(self.log_occupancy) - 1}, target={self.target}, log_evidence={self.log_evidence!r}, "
+                f"n_nan_windows={self.n_nan_windows})")
+
+    def pmf(self):
+        """ (T + 1,) P(N = n | data): the last states summed in ascending order """
+        return np.exp(self.log_occupancy).sum(axis=1)
+
+    def cdf(self):
+        """ (T + 1,) P(N <= n | data), the running sum of `pmf` """
+        return np.cumsum(self.pmf())
+
+    def mean(self):
+        """ the posterior mean of N, in frames: the sum of `exact_dwell`'s marginals over the set """
+        return float(np.arange(len(self.log_occupancy)) @ self.pmf())
+
+    def var(self):
+        """ the posterior variance of N, in frames squared, about `mean` """
+        pmf, n = self.pmf(), np.arange(len(self.log_occupancy))
+        return float((n - n @ pmf) ** 2 @ pmf)
+
+    def interval(self, level=0.95):
+        """
+        the central interval (lo, hi) in frames: lo the smallest n whose cdf reaches (1 - level) / 2, hi the smallest whose cdf
+        reaches 1 - (1 - level) / 2 (T where rounding keeps the cdf below it)
+        """
+        if not 0 < level < 1:
+            raise ValueError(f"level = {level!r}: a probability strictly between 0 and 1")
+        cdf = self.cdf()
+        if np.any(np.isnan(cdf)):
+            raise ValueError("the result is NaN: no interval")
+        tail = (1 - level) / 2
+        lo, hi = (min(int(np.searchsorted(cdf, q, side='left')), len(cdf) - 1) for q in (tail, 1 - tail))
+        return lo, hi
+
+    def fraction(self):
+        """ (T + 1,) the grid n / T that `pmf` lives on: the looped fraction of the trajectory """
+        T = len(self.log_occupancy) - 1
+        return np.arange(T + 1) / max(T, 1)
+
+
+def exact_dwell_occupancy(trajs, model, prior, target, nan='propagate', scratch_bytes=0):
+    """
+    The exact posterior distribution of the number of frames that a `GenericGaussianModel` profile spends in the states
+    `target` under a dwell-time prior, jointly with the last state: the forward recursion of `exact_dwell` resolved by that
+    number, one device launch per end frame (bild_gauss_dwell_occupancy).  No draws, no histogram noise
+    in the tails that a credible interval is read from.
+
+    trajs, model, prior, nan, scratch_bytes : as for `exact_dwell`; a list gives a list of results from ONE device call.  A
+        trajectory of a chunk costs S T (T + 1) doubles of the longest T beside `exact_dwell`'s forward tables
+    target : a state or a collection of states, a non-empty proper subset of the model's (so a model of one state is refused)
+
+    Every refusal is `exact_dwell`'s or the target's (ValueError) and is raised before the trajectories are uploaded.
+    Returns `DwellOccupancy` or a list of them.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    states = _target_states(target, model.msd.shape[0])
+    if not items:
+        return []
+    ts = model.trajset(items[0] if single else items)
+    res = _lib.gauss_dwell_occupancy(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
+                                     sum(1 << s for s in states), omit=nan == 'omit', scratch_bytes=scratch_bytes)
+    out = [DwellOccupancy(traj=t, model=model, prior=prior, nan=nan, target=states, log_evidence=float(res['logev'][j]),
+                          n_nan_windows=int(res['n_nan_windows'][j]), log_occupancy=res['log_occ'][j, :len(t) + 1].copy())
+           for j, t in enumerate(items)]
+    return out[0] if single else out
+
+
+def pooled_occupancy(results):
+    """
+    (sum_j T_j + 1,) the pmf of the total number of frames in the target set over several trajectories' `DwellOccupancy`: given
+    model and prior their posteriors are independent, so it is the convolution of their pmfs, in linear space and in the order
+    of the list (host only).  Refused (ValueError): an empty list, differing targets, a result that is NaN.
+    """
+    results = list(results)
+    if not results:
+        raise ValueError("no result to pool")
+    if any(r.target != results[0].target for r in results):
+        raise ValueError(f"the results have differing targets: {sorted(set(r.target for r in results))}")
+    total = np.ones(1)
+    for j, r in enumerate(results):
+        pmf = r.pmf()
+        if np.any(np.isnan(pmf)):
+            raise ValueError(f"result {j} is NaN (n_nan_windows = {r.n_nan_windows}, log_evidence = {r.log_evidence!r})")
+        total = np.convolve(total, pmf)
+    return total
 
 
 def _hazard_edges(edges, n):

@@ -1307,6 +1307,41 @@ int bild_gauss_dwell_first_contact(const bild_gauss_model *m, const bild_gauss_t
                                    const double *log_jump, const double *log_dwell, const double *log_surv, int T_max,
                                    unsigned target, unsigned flags, int64_t scratch_bytes, bild_dwell_first_contact_out *out);
 
+/* ---------------------------------------------------------------- looped time under a dwell-time prior ----
+ * GenericGaussianModel only, at most 4 states.  The exact posterior distribution of the number N of
+ * frames t with theta_t in the set G (bit s of target: state s belongs to G), jointly with the last state, under the
+ * dwell-time prior of bild_gauss_dwell_evidence (same tables, same NaN flag).  Every frame counts, observed or missing.  That
+ * block's forward recursion resolved by n, with g_s = 1 for s in G and 0 otherwise:
+ *   A(b, s, n)     = [n = g_s b] (log_init[s] + omega_s(0, b) + F[s][b])
+ *                    (+) log sum_{c = 1 .. b - 1} exp(alpha(c, s, n - g_s (b - c)) + omega_s(c, b) + W[s][c - 1][b])
+ *   alpha(c, s, n) = log sum_s' exp(A(c, s', n) + log_jump[s'][s])                                  (1 <= c < T, 0 <= n <= c)
+ * A segment outside G keeps n, a segment inside G adds its length; alpha(c, ., n) is empty outside 0 <= n <= c.  The shifted
+ * index couples every n of every earlier c: one launch per end frame b, alpha kept for every c, S T_longest (T_longest + 1)
+ * doubles per trajectory of a chunk beside the forward tables (16 MB at T = 1000 and 2 states).  Per trajectory of T frames:
+ *   logev, n_nan_windows   as bild_gauss_dwell_evidence gives them, bit for bit: the same forward kernel on the same tables
+ *   log_occ        (T_max + 1) x S: entry [n][s] = A(T, s, n) - logev = log P(N = n, theta_{T-1} = s | x); -inf where the
+ *                  probability is 0, and -inf for n > T
+ * Every entry is normalised by logev of the ordinary forward pass, not by their sum: sum exp(log_occ) = 1 holds up to rounding
+ * and is a check, not a construction.  A NaN window enters no sum.  flags = 0 (BILD_DWELL_NAN_PROPAGATE): a trajectory with
+ * n_nan_windows > 0 has NaN in logev and log_occ; the other trajectories are untouched.  BILD_DWELL_NAN_OMIT: the skipped
+ * windows weigh 0.  A trajectory without a profile of positive weight has logev -inf and NaN in log_occ.  The switch frames c
+ * of an entry are summed by eight waves, wave q taking c = c0 + q, c0 + q + 8, .. in ascending order from the first c0 that can
+ * reach the entry's tile of 64 values of n, the waves merged in wave order: no atomics, fixed summation orders that depend on
+ * the trajectory alone, so results are bit-identical across calls, the order of the set, a trajectory alone or in a batch, and
+ * scratch_bytes (chunks of whole trajectories; 0: at most 1 GiB and a third of the free device memory).  Refused before any
+ * device work: what bild_gauss_dwell_evidence refuses, and a target that is empty, names a state the model does not have or
+ * holds every state (BILD_ERR_INVALID): a model of one state is always refused.  Plain launches on the set's stream.
+ * Synchronous. */
+typedef struct bild_dwell_occupancy_out {
+    double *logev;                          /* n_traj */
+    int64_t *n_nan_windows;                 /* n_traj */
+    double *log_occ;                        /* n_traj x (T_max + 1) x S */
+} bild_dwell_occupancy_out;                 /* every pointer may be NULL: not written */
+
+int bild_gauss_dwell_occupancy(const bild_gauss_model *m, const bild_gauss_trajset *ts, int L, const double *log_init,
+                               const double *log_jump, const double *log_dwell, const double *log_surv, int T_max,
+                               unsigned target, unsigned flags, int64_t scratch_bytes, bild_dwell_occupancy_out *out);
+
 #ifdef __cplusplus
 }
 #endif
