@@ -1249,6 +1249,22 @@ def interval_marginals(seg_start, seg_state, w, n, T):
     return post
 
 
+# ---------------------------------------------------------------- the exact-inference calls
+# Each call fills the arrays of a ``bild_*_out`` structure of pointers.  A wrapper allocates them as a dict whose keys are the
+# structure's fields, in the header's order; `_out` turns the dict into the structure.  The dwell-time calls that share one
+# argument order go through `_dwell_call`.  (tests/test_abi_header.py holds the structures, `_SIGNATURES` and the positions of
+# the wrappers' arguments to include/bild_amd.h without a device.)
+
+def _out(cls, res, null_empty=False, rename={}):
+    """
+    the ``bild_*_out`` structure ``cls`` of a call from its dict of output arrays, key = field (``rename``: keys that differ).
+    None becomes NULL: not written.  ``null_empty`` is the rule of the sensitivity calls, which pass an empty array (grad and
+    fisher at P = 0) as NULL too.  Elsewhere an empty array keeps its address: NULL means "not asked for" there (a NULL
+    log_post is the forward pass alone), also at T_max = 0.
+    """
+    return cls(**{rename.get(name, name): (None if a is None or (null_empty and not a.size) else aptr(a)) for name, a in res.items()})
+
+
 class ExactOut(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'kl', 'map_logl', 'map_seg_start', 'map_seg_state', 'n_nan',
                                                       'log_post')]
@@ -1282,7 +1298,7 @@ def exact_evidence(model, ts, k, transitions, marginals=True, max_profiles=2 ** 
            'map_seg_start': np.empty((n, K1), dtype=np.int32), 'map_seg_state': np.empty((n, K1), dtype=np.int32),
            'n_nan': np.empty(n, dtype=np.int64),
            'log_post': np.empty((n, model.S, T_max)) if marginals else None}
-    spec = ExactOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
+    spec = _out(ExactOut, res)
     if gauss:
         check(lib().bild_gauss_exact_evidence(model._h, ts._h, int(k), aptr(tr), float(max_profiles), int(scratch_bytes), T_max,
                                               ctypes.byref(spec)))
@@ -1313,7 +1329,7 @@ def gauss_segment_evidence(model, ts, k_max, transitions, marginals=True, omit=F
            'n_profiles': np.empty((n, K)), 'n_omitted': np.empty((n, K)),
            'map_seg_start': np.empty((n, K, K), dtype=np.int32), 'map_seg_state': np.empty((n, K, K), dtype=np.int32),
            'log_post': np.empty((n, K, model.S, T_max)) if marginals else None}
-    spec = SegdpOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
+    spec = _out(SegdpOut, res)
     check(lib().bild_gauss_segment_evidence(model._h, ts._h, int(k_max), aptr(tr), T_max, SEGDP_NAN_OMIT if omit else SEGDP_NAN_PROPAGATE,
                                             int(scratch_bytes), ctypes.byref(spec)))
     return res
@@ -1338,8 +1354,7 @@ def gauss_segment_draw(model, ts, k_max, transitions, draw_traj, draw_k, uniform
         assert uniforms.shape == (n, U)
     res = {'seg_start': np.empty((n, K), dtype=np.int32), 'seg_state': np.empty((n, K), dtype=np.int32), 'logl': np.empty(n),
            'uniforms': np.zeros((n, U))}
-    spec = SegdrawOut(seg_start=aptr(res['seg_start']), seg_state=aptr(res['seg_state']), logl=aptr(res['logl']),
-                      uniforms_out=aptr(res['uniforms']))
+    spec = _out(SegdrawOut, res, rename={'uniforms': 'uniforms_out'})
     check(lib().bild_gauss_segment_draw(model._h, ts._h, int(k_max), aptr(tr), int(np.max(ts.T)), int(scratch_bytes), n, iptr(draw_traj),
                                         iptr(draw_k), None if uniforms is None else aptr(uniforms), int(seed) & (2 ** 64 - 1),
                                         ctypes.byref(spec)))
@@ -1368,7 +1383,7 @@ def gauss_segment_sensitivities(model, ts, trajs, k_max, transitions, log_k_prio
     derivs, keep = _gauss_derivs(model, P, dmsd, dmsd_inf, dmean)
     res = {'logev': np.empty((n, K)), 'log_marginal': np.empty(n), 'k_post': np.empty((n, K)), 'grad': np.empty((n, P)),
            'exp_logl': np.empty(n), 'fisher': np.empty((n, P, P)) if fisher else None}
-    spec = SegsensOut(**{name: (aptr(a) if a is not None and a.size else None) for name, a in res.items()})
+    spec = _out(SegsensOut, res, null_empty=True)
     check(lib().bild_gauss_segment_sensitivities(model._h, ts._h, dptr(x), int(k_max), aptr(tr), SEGDP_NAN_OMIT if omit else SEGDP_NAN_PROPAGATE,
                                                  None if prior is None else dptr(prior), int(P), ctypes.byref(derivs),
                                                  int(scratch_bytes), ctypes.byref(spec)))
@@ -1392,24 +1407,34 @@ def _dwell_tables(model, log_init, log_jump, log_dwell, log_surv):
     return (log_init, log_jump, log_dwell, log_surv), L
 
 
+def _dwell_call(name, out_cls, model, ts, tables, outputs, scalars=(), omit=False, scratch_bytes=0):
+    """
+    the path of the dwell-time calls with the argument order (m, ts, L, the four tables, T_max, the call's own integer scalars,
+    flags, scratch_bytes, out): ``name`` the library's function, ``tables`` as `_dwell_tables` takes them, ``outputs(n, S,
+    T_max)`` the dict of the output arrays (keys: the fields of ``out_cls``; None: not computed), which is returned
+    """
+    tables, L = _dwell_tables(model, *tables)
+    T_max = int(np.max(ts.T))
+    res = outputs(ts.n_traj, model.S, T_max)
+    spec = _out(out_cls, res)
+    check(getattr(lib(), name)(model._h, ts._h, L, *[dptr(a) for a in tables], T_max, *[int(v) for v in scalars],
+                               DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
+    return res
+
+
 def gauss_dwell_evidence(model, ts, log_init, log_jump, log_dwell, log_surv, marginals=True, omit=False, scratch_bytes=0):
     """
     exact inference under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_evidence): a dict of logev,
     map_logjoint (n_traj,), map_states (n_traj, T_max) uint8, n_nan_windows (n_traj,) int64 and, with marginals, log_post
     (n_traj, S, T_max), exp_jumps (n_traj, S, S) and exp_stay (n_traj, S) (None without); T_max the set's longest trajectory
     """
-    S = model.S
-    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
-    n = ts.n_traj
-    T_max = int(np.max(ts.T))
-    res = {'logev': np.empty(n), 'map_logjoint': np.empty(n), 'map_states': np.empty((n, T_max), dtype=np.uint8),
-           'n_nan_windows': np.empty(n, dtype=np.int64),
-           'log_post': np.empty((n, S, T_max)) if marginals else None,
-           'exp_jumps': np.empty((n, S, S)) if marginals else None, 'exp_stay': np.empty((n, S)) if marginals else None}
-    spec = DwellOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
-    check(lib().bild_gauss_dwell_evidence(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
-                                          DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
-    return res
+    outputs = lambda n, S, T_max: {
+        'logev': np.empty(n), 'map_logjoint': np.empty(n), 'map_states': np.empty((n, T_max), dtype=np.uint8),
+        'n_nan_windows': np.empty(n, dtype=np.int64),
+        'log_post': np.empty((n, S, T_max)) if marginals else None,
+        'exp_jumps': np.empty((n, S, S)) if marginals else None, 'exp_stay': np.empty((n, S)) if marginals else None}
+    return _dwell_call('bild_gauss_dwell_evidence', DwellOut, model, ts, (log_init, log_jump, log_dwell, log_surv), outputs,
+                       omit=omit, scratch_bytes=scratch_bytes)
 
 
 class DwellsensOut(ctypes.Structure):
@@ -1431,7 +1456,7 @@ def gauss_dwell_sensitivities(model, ts, trajs, log_init, log_jump, log_dwell, l
     derivs, keep = _gauss_derivs(model, P, dmsd, dmsd_inf, dmean)
     res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'grad': np.empty((n, P)), 'exp_logl': np.empty(n),
            'fisher': np.empty((n, P, P)) if fisher else None}
-    spec = DwellsensOut(**{name: (aptr(a) if a is not None and a.size else None) for name, a in res.items()})
+    spec = _out(DwellsensOut, res, null_empty=True)
     check(lib().bild_gauss_dwell_sensitivities(model._h, ts._h, dptr(x), L, dptr(log_init), dptr(log_jump), dptr(log_dwell),
                                                dptr(log_surv), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(P),
                                                ctypes.byref(derivs), int(scratch_bytes), ctypes.byref(spec)))
@@ -1448,16 +1473,11 @@ def gauss_dwell_lengths(model, ts, log_init, log_jump, log_dwell, log_surv, omit
     of logev (n_traj,), n_nan_windows (n_traj,) int64, exp_jumps (n_traj, S, S), exp_init (n_traj, S), exp_dwell and exp_cens
     (n_traj, S, T_max), length l at column l - 1, 0 behind a trajectory's T; T_max the set's longest trajectory
     """
-    S = model.S
-    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
-    n = ts.n_traj
-    T_max = int(np.max(ts.T))
-    res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'exp_jumps': np.empty((n, S, S)),
-           'exp_init': np.empty((n, S)), 'exp_dwell': np.empty((n, S, T_max)), 'exp_cens': np.empty((n, S, T_max))}
-    spec = DwellLengthsOut(**{name: aptr(a) for name, a in res.items()})
-    check(lib().bild_gauss_dwell_lengths(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
-                                         DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
-    return res
+    outputs = lambda n, S, T_max: {
+        'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'exp_jumps': np.empty((n, S, S)),
+        'exp_init': np.empty((n, S)), 'exp_dwell': np.empty((n, S, T_max)), 'exp_cens': np.empty((n, S, T_max))}
+    return _dwell_call('bild_gauss_dwell_lengths', DwellLengthsOut, model, ts, (log_init, log_jump, log_dwell, log_surv), outputs,
+                       omit=omit, scratch_bytes=scratch_bytes)
 
 
 class DwellSwitchCountsOut(ctypes.Structure):
@@ -1469,17 +1489,11 @@ def gauss_dwell_switch_counts(model, ts, log_init, log_jump, log_dwell, log_surv
     exact posterior switch counts under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_switch_counts): a
     dict of logev, log_tail (n_traj,), n_nan_windows (n_traj,) int64 and log_count (n_traj, k_max + 1, S)
     """
-    S = model.S
-    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
-    n = ts.n_traj
-    T_max = int(np.max(ts.T))
-    res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_count': np.empty((n, max(int(k_max), -1) + 1, S)),
-           'log_tail': np.empty(n)}     # (a negative k_max: no column, and the call refuses it)
-    spec = DwellSwitchCountsOut(**{name: aptr(a) for name, a in res.items()})
-    check(lib().bild_gauss_dwell_switch_counts(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
-                                               int(k_max), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes),
-                                               ctypes.byref(spec)))
-    return res
+    outputs = lambda n, S, T_max: {
+        'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_count': np.empty((n, max(int(k_max), -1) + 1, S)),
+        'log_tail': np.empty(n)}        # (a negative k_max: no column, and the call refuses it)
+    return _dwell_call('bild_gauss_dwell_switch_counts', DwellSwitchCountsOut, model, ts, (log_init, log_jump, log_dwell, log_surv),
+                       outputs, scalars=(k_max,), omit=omit, scratch_bytes=scratch_bytes)
 
 
 class DwellFirstContactOut(ctypes.Structure):
@@ -1492,15 +1506,10 @@ def gauss_dwell_first_contact(model, ts, log_init, log_jump, log_dwell, log_surv
     target the bit mask of the states of the set: a dict of logev, log_never (n_traj,), n_nan_windows (n_traj,) int64 and
     log_first (n_traj, T_max), NaN behind a trajectory's T; T_max the set's longest trajectory
     """
-    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
-    n = ts.n_traj
-    T_max = int(np.max(ts.T))
-    res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_first': np.empty((n, T_max)), 'log_never': np.empty(n)}
-    spec = DwellFirstContactOut(**{name: aptr(a) for name, a in res.items()})
-    check(lib().bild_gauss_dwell_first_contact(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
-                                               int(target), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes),
-                                               ctypes.byref(spec)))
-    return res
+    outputs = lambda n, S, T_max: {
+        'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_first': np.empty((n, T_max)), 'log_never': np.empty(n)}
+    return _dwell_call('bild_gauss_dwell_first_contact', DwellFirstContactOut, model, ts, (log_init, log_jump, log_dwell, log_surv),
+                       outputs, scalars=(target,), omit=omit, scratch_bytes=scratch_bytes)
 
 
 class DwellOccupancyOut(ctypes.Structure):
@@ -1513,16 +1522,10 @@ def gauss_dwell_occupancy(model, ts, log_init, log_jump, log_dwell, log_surv, ta
     (bild_gauss_dwell_occupancy), target the bit mask of the states of the set: a dict of logev (n_traj,), n_nan_windows
     (n_traj,) int64 and log_occ (n_traj, T_max + 1, S), -inf behind a trajectory's T; T_max the set's longest trajectory
     """
-    S = model.S
-    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
-    n = ts.n_traj
-    T_max = int(np.max(ts.T))
-    res = {'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_occ': np.empty((n, T_max + 1, S))}
-    spec = DwellOccupancyOut(**{name: aptr(a) for name, a in res.items()})
-    check(lib().bild_gauss_dwell_occupancy(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
-                                           int(target), DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes),
-                                           ctypes.byref(spec)))
-    return res
+    outputs = lambda n, S, T_max: {
+        'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_occ': np.empty((n, T_max + 1, S))}
+    return _dwell_call('bild_gauss_dwell_occupancy', DwellOccupancyOut, model, ts, (log_init, log_jump, log_dwell, log_surv), outputs,
+                       scalars=(target,), omit=omit, scratch_bytes=scratch_bytes)
 
 
 class DwellFilterOut(ctypes.Structure):
@@ -1535,17 +1538,12 @@ def gauss_dwell_filter(model, ts, log_init, log_jump, log_dwell, log_surv, run_m
     (n_traj,), prefix_logev and run_mean (n_traj, T_max), log_filtered (n_traj, S, T_max), n_nan_windows (n_traj, T_max) int64
     and, with run_max > 0, log_run (n_traj, S, T_max, run_max) (None without); T_max the set's longest trajectory
     """
-    S = model.S
-    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
-    n, R = ts.n_traj, int(run_max)
-    T_max = int(np.max(ts.T))
-    res = {'logev': np.empty(n), 'prefix_logev': np.empty((n, T_max)), 'log_filtered': np.empty((n, S, T_max)),
-           'run_mean': np.empty((n, T_max)), 'log_run': np.empty((n, S, T_max, R)) if R > 0 else None,
-           'n_nan_windows': np.empty((n, T_max), dtype=np.int64)}
-    spec = DwellFilterOut(**{name: (aptr(a) if a is not None else None) for name, a in res.items()})
-    check(lib().bild_gauss_dwell_filter(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max, R,
-                                        DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
-    return res
+    outputs = lambda n, S, T_max: {
+        'logev': np.empty(n), 'prefix_logev': np.empty((n, T_max)), 'log_filtered': np.empty((n, S, T_max)),
+        'run_mean': np.empty((n, T_max)), 'log_run': np.empty((n, S, T_max, int(run_max))) if int(run_max) > 0 else None,
+        'n_nan_windows': np.empty((n, T_max), dtype=np.int64)}
+    return _dwell_call('bild_gauss_dwell_filter', DwellFilterOut, model, ts, (log_init, log_jump, log_dwell, log_surv), outputs,
+                       scalars=(run_max,), omit=omit, scratch_bytes=scratch_bytes)
 
 
 DWELL_LAG_MAX = 63      # BILD_DWELL_LAG_MAX: a window of lag + 1 frames is one wavefront
@@ -1560,16 +1558,11 @@ def gauss_dwell_lag(model, ts, log_init, log_jump, log_dwell, log_surv, lag, omi
     exact fixed-lag smoothing under a dwell-time prior for every trajectory of the set (bild_gauss_dwell_lag): a dict of logev
     (n_traj,), log_lagged (n_traj, S, T_max, lag + 1) and n_nan_windows (n_traj, T_max) int64; T_max the set's longest trajectory
     """
-    S = model.S
-    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
-    n, lag = ts.n_traj, int(lag)
-    T_max = int(np.max(ts.T))
-    res = {'logev': np.empty(n), 'log_lagged': np.empty((n, S, T_max, max(lag, 0) + 1)),
-           'n_nan_windows': np.empty((n, T_max), dtype=np.int64)}
-    spec = DwellLagOut(**{name: aptr(a) for name, a in res.items()})
-    check(lib().bild_gauss_dwell_lag(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max, lag,
-                                     DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, int(scratch_bytes), ctypes.byref(spec)))
-    return res
+    outputs = lambda n, S, T_max: {
+        'logev': np.empty(n), 'log_lagged': np.empty((n, S, T_max, max(int(lag), 0) + 1)),
+        'n_nan_windows': np.empty((n, T_max), dtype=np.int64)}
+    return _dwell_call('bild_gauss_dwell_lag', DwellLagOut, model, ts, (log_init, log_jump, log_dwell, log_surv), outputs,
+                       scalars=(lag,), omit=omit, scratch_bytes=scratch_bytes)
 
 
 class DwelldrawOut(ctypes.Structure):
@@ -1599,9 +1592,7 @@ def gauss_dwell_draw(model, ts, log_init, log_jump, log_dwell, log_surv, draw_tr
     T_max = int(np.max(ts.T))
     res = {'states': np.empty((n, T_max), dtype=np.uint8), 'n_switches': np.empty(n, dtype=np.int32), 'logl': np.empty(n),
            'log_prior': np.empty(n), 'n_uniforms': np.empty(n, dtype=np.int32), 'uniforms': np.zeros((n, U)) if U > 0 else None}
-    spec = DwelldrawOut(states=aptr(res['states']), n_switches=aptr(res['n_switches']), logl=aptr(res['logl']),
-                        log_prior=aptr(res['log_prior']), n_uniforms=aptr(res['n_uniforms']),
-                        uniforms_out=None if res['uniforms'] is None else aptr(res['uniforms']))
+    spec = _out(DwelldrawOut, res, rename={'uniforms': 'uniforms_out'})
     check(lib().bild_gauss_dwell_draw(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
                                       int(scratch_bytes), n, iptr(draw_traj), None if draw_stream is None else aptr(draw_stream), U,
                                       None if uniforms is None else aptr(uniforms), int(seed) & (2 ** 64 - 1), ctypes.byref(spec)))

@@ -55,7 +55,17 @@ from .profiles import Loopingprofile, segments_from_states, states_from_segments
 MAX_K = 15
 
 
-class ExactResult:
+class _Record:
+    """ the base of the result classes: the attributes are the class's ``__slots__``, each given by keyword (KeyError without one) """
+
+    __slots__ = ()
+
+    def __init__(self, **kw):
+        for name in self.__slots__:
+            setattr(self, name, kw[name])
+
+
+class ExactResult(_Record):
     """
     The exact answer for one trajectory and one k.
 
@@ -70,10 +80,6 @@ class ExactResult:
     """
 
     __slots__ = ('k', 'n_profiles', 'logev', 'KL', 'n_nan', 'map_profile', 'map_logL', 'log_marginal_posterior')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return (f"ExactResult(k={self.k}, n_profiles={self.n_profiles}, logev={self.logev!r}, KL={self.KL!r}, "
@@ -479,7 +485,7 @@ def exact_draw(results, n, k=None, dE=None, seed=0, uniforms=None, scratch_bytes
 
 # ---------------------------------------------------------------- gradient of the exact evidence (section 20)
 
-class EvidenceSensitivities:
+class EvidenceSensitivities(_Record):
     """
     `exact_sensitivities` of n trajectories, K = k_max + 1 and P parameters:
 
@@ -495,10 +501,6 @@ class EvidenceSensitivities:
     """
 
     __slots__ = ('log_marginal', 'k_posterior', 'logev', 'grad', 'expected_logL', 'fisher')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return f"EvidenceSensitivities(n={len(self.log_marginal)}, K={self.logev.shape[1]}, P={self.grad.shape[1]})"
@@ -616,6 +618,10 @@ class DwellPrior:
         """ the longest trajectory the tables serve """
         return self.log_dwell.shape[1]
 
+    def tables(self):
+        """ (log_init, log_jump, log_dwell, log_surv): the order in which the `_lib.gauss_dwell_*` calls take them """
+        return self.log_init, self.log_jump, self.log_dwell, self.log_surv
+
     def __repr__(self):
         return f"DwellPrior(S={self.nStates}, L={self.L})"
 
@@ -712,7 +718,7 @@ class DwellPrior:
         return float(total)
 
 
-class ExactDwellResults:
+class ExactDwellResults(_Record):
     """
     `exact_dwell` of one trajectory.
 
@@ -729,10 +735,6 @@ class ExactDwellResults:
 
     __slots__ = ('traj', 'model', 'prior', 'nan', 'log_evidence', 'map_profile', 'map_log_joint', 'log_marginal_posterior',
                  'expected_jumps', 'expected_stay', 'n_nan_windows')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return (f"ExactDwellResults(T={len(self.traj)}, log_evidence={self.log_evidence!r}, map_log_joint={self.map_log_joint!r}, "
@@ -777,19 +779,21 @@ def _check_exact_dwell(trajs, model, prior, nan):
     return single, items
 
 
-def _dwell_results(items, model, prior, nan, res):
-    out = []
-    for j, t in enumerate(items):
-        T = len(t)
-        states = res['map_states'][j, :T]
-        profile = None if T == 0 or states[0] == 255 else Loopingprofile(states.astype(int))
-        marg = res['log_post'] is not None
-        out.append(ExactDwellResults(
-            traj=t, model=model, prior=prior, nan=nan, log_evidence=float(res['logev'][j]), map_profile=profile,
-            map_log_joint=float(res['map_logjoint'][j]), log_marginal_posterior=res['log_post'][j, :, :T].copy() if marg else None,
-            expected_jumps=res['exp_jumps'][j].copy() if marg else None, expected_stay=res['exp_stay'][j].copy() if marg else None,
-            n_nan_windows=int(res['n_nan_windows'][j])))
-    return out
+def _dwell_per_trajectory(call, cls, single, items, model, prior, nan, fields, *scalars, **options):
+    """
+    What the `exact_dwell*` entry points share behind their refusals, (single, items) as `_check_exact_dwell` returns them.
+    Without items the answer is [] and nothing is uploaded; else ONE trajectory set of them and ONE ``call`` -- a
+    `_lib.gauss_dwell_*` -- on it with the prior's tables, the entry point's own ``scalars`` and ``options``.  Trajectory j
+    becomes a ``cls`` of traj, model, prior, nan, log_evidence and the entry point's own ``fields(res, j, T)``; a single
+    trajectory gives its result, a list a list.
+    """
+    if not items:
+        return []
+    ts = model.trajset(items[0] if single else items)
+    res = call(model.handle(), ts, *prior.tables(), *scalars, omit=nan == 'omit', **options)
+    out = [cls(traj=t, model=model, prior=prior, nan=nan, log_evidence=float(res['logev'][j]), **fields(res, j, len(t)))
+           for j, t in enumerate(items)]
+    return out[0] if single else out
 
 
 def exact_dwell(trajs, model, prior, marginals=True, nan='propagate', scratch_bytes=0):
@@ -815,18 +819,21 @@ def exact_dwell(trajs, model, prior, marginals=True, nan='propagate', scratch_by
     `ExactDwellResults` or a list of them.
     """
     single, items = _check_exact_dwell(trajs, model, prior, nan)
-    if not items:
-        return []
-    ts = model.trajset(items[0] if single else items)
-    res = _lib.gauss_dwell_evidence(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
-                                    marginals=marginals, omit=nan == 'omit', scratch_bytes=scratch_bytes)
-    out = _dwell_results(items, model, prior, nan, res)
-    return out[0] if single else out
+
+    def fields(res, j, T):
+        states = res['map_states'][j, :T]
+        marg = res['log_post'] is not None
+        return dict(map_profile=None if T == 0 or states[0] == 255 else Loopingprofile(states.astype(int)),
+                    map_log_joint=float(res['map_logjoint'][j]), log_marginal_posterior=res['log_post'][j, :, :T].copy() if marg else None,
+                    expected_jumps=res['exp_jumps'][j].copy() if marg else None, expected_stay=res['exp_stay'][j].copy() if marg else None,
+                    n_nan_windows=int(res['n_nan_windows'][j]))
+    return _dwell_per_trajectory(_lib.gauss_dwell_evidence, ExactDwellResults, single, items, model, prior, nan, fields,
+                                 marginals=marginals, scratch_bytes=scratch_bytes)
 
 
 # ---------------------------------------------------------------- online filtering under the dwell-time prior (section 25)
 
-class DwellFilterResults:
+class DwellFilterResults(_Record):
     """
     `exact_dwell_filter` of one trajectory of T frames: at frame t, what `exact_dwell` says about the truncation x[:t + 1].
 
@@ -851,10 +858,6 @@ class DwellFilterResults:
     __slots__ = ('traj', 'model', 'prior', 'nan', 'log_evidence', 'prefix_log_evidence', 'log_predictive', 'log_filtered',
                  'run_length_mean', 'log_run_length', 'n_nan_windows')
 
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
-
     def __repr__(self):
         return f"DwellFilterResults(T={len(self.traj)}, log_evidence={self.log_evidence!r})"
 
@@ -875,23 +878,17 @@ def exact_dwell_filter(trajs, model, prior, run_max=0, nan='propagate', scratch_
     single, items = _check_exact_dwell(trajs, model, prior, nan)
     if int(run_max) != run_max or run_max < 0:
         raise ValueError(f"run_max = {run_max!r}: an integer >= 0")
-    if not items:
-        return []
-    ts = model.trajset(items[0] if single else items)
-    res = _lib.gauss_dwell_filter(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
-                                  run_max=int(run_max), omit=nan == 'omit', scratch_bytes=scratch_bytes)
-    out = []
-    for j, t in enumerate(items):
-        T = len(t)
+
+    def fields(res, j, T):
         prefix = res['prefix_logev'][j, :T].copy()
         with np.errstate(invalid='ignore'):
             predictive = np.diff(prefix, prepend=0.0)
-        out.append(DwellFilterResults(
-            traj=t, model=model, prior=prior, nan=nan, log_evidence=float(res['logev'][j]), prefix_log_evidence=prefix,
-            log_predictive=predictive, log_filtered=res['log_filtered'][j, :, :T].copy(), run_length_mean=res['run_mean'][j, :T].copy(),
-            log_run_length=None if res['log_run'] is None else res['log_run'][j, :, :T].copy(),
-            n_nan_windows=res['n_nan_windows'][j, :T].copy()))
-    return out[0] if single else out
+        return dict(prefix_log_evidence=prefix, log_predictive=predictive, log_filtered=res['log_filtered'][j, :, :T].copy(),
+                    run_length_mean=res['run_mean'][j, :T].copy(),
+                    log_run_length=None if res['log_run'] is None else res['log_run'][j, :, :T].copy(),
+                    n_nan_windows=res['n_nan_windows'][j, :T].copy())
+    return _dwell_per_trajectory(_lib.gauss_dwell_filter, DwellFilterResults, single, items, model, prior, nan, fields,
+                                 run_max=int(run_max), scratch_bytes=scratch_bytes)
 
 
 # ---------------------------------------------------------------- fixed-lag smoothing under the dwell-time prior (section 26)
@@ -899,7 +896,7 @@ def exact_dwell_filter(trajs, model, prior, run_max=0, nan='propagate', scratch_
 MAX_DWELL_LAG = _lib.DWELL_LAG_MAX
 
 
-class DwellLagResults:
+class DwellLagResults(_Record):
     """
     `exact_dwell_lag` of one trajectory of T frames: at frame t and lag l, what `exact_dwell` says about frame t of the
     truncation x[:t + l + 1].
@@ -916,10 +913,6 @@ class DwellLagResults:
     """
 
     __slots__ = ('traj', 'model', 'prior', 'nan', 'lag', 'log_evidence', 'log_lagged', 'n_nan_windows')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return f"DwellLagResults(T={len(self.traj)}, lag={self.lag}, log_evidence={self.log_evidence!r})"
@@ -973,18 +966,10 @@ def exact_dwell_lag(trajs, model, prior, lag, nan='propagate', scratch_bytes=0):
         raise ValueError(f"lag = {lag!r}: an integer >= 0")
     if lag > MAX_DWELL_LAG:
         raise ValueError(f"lag = {lag}: at most {MAX_DWELL_LAG}")
-    if not items:
-        return []
-    ts = model.trajset(items[0] if single else items)
-    res = _lib.gauss_dwell_lag(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv, int(lag),
-                               omit=nan == 'omit', scratch_bytes=scratch_bytes)
-    out = []
-    for j, t in enumerate(items):
-        T = len(t)
-        out.append(DwellLagResults(
-            traj=t, model=model, prior=prior, nan=nan, lag=int(lag), log_evidence=float(res['logev'][j]),
-            log_lagged=res['log_lagged'][j, :, :T].copy(), n_nan_windows=res['n_nan_windows'][j, :T].copy()))
-    return out[0] if single else out
+    fields = lambda res, j, T: dict(lag=int(lag), log_lagged=res['log_lagged'][j, :, :T].copy(),
+                                    n_nan_windows=res['n_nan_windows'][j, :T].copy())
+    return _dwell_per_trajectory(_lib.gauss_dwell_lag, DwellLagResults, single, items, model, prior, nan, fields, int(lag),
+                                 scratch_bytes=scratch_bytes)
 
 
 # ---------------------------------------------------------------- profiles drawn under the dwell-time prior (section 22)
@@ -1127,9 +1112,8 @@ def exact_dwell_draw(results, n, seed=0, uniforms=None, keep_uniforms=0, scratch
                                np.zeros(0), np.zeros((0, U)) if U else None) for r in items]
         return out[0] if single else out
     ts = model.trajset(items[0].traj if single else [r.traj for r in items])
-    res = _lib.gauss_dwell_draw(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
-                                np.repeat(np.arange(len(items)), n), uniforms=uniforms, keep_uniforms=U, seed=seed,
-                                scratch_bytes=scratch_bytes)
+    res = _lib.gauss_dwell_draw(model.handle(), ts, *prior.tables(), np.repeat(np.arange(len(items)), n), uniforms=uniforms,
+                                keep_uniforms=U, seed=seed, scratch_bytes=scratch_bytes)
     short = np.flatnonzero(res['n_uniforms'] < 0)
     if len(short):
         j, i = divmod(int(short[0]), n)
@@ -1144,7 +1128,7 @@ def exact_dwell_draw(results, n, seed=0, uniforms=None, keep_uniforms=0, scratch
     return out[0] if single else out
 
 
-class MarkovPriorFit:
+class MarkovPriorFit(_Record):
     """
     `fit_markov_prior`'s result: P (S, S) and init (S,), the total log evidence of the data set at every iteration's
     parameters (`log_evidence`, one entry per device call; the last belongs to the parameters one M-step before P),
@@ -1152,10 +1136,6 @@ class MarkovPriorFit:
     """
 
     __slots__ = ('P', 'init', 'log_evidence', 'n_iter', 'converged')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return f"MarkovPriorFit(n_iter={self.n_iter}, converged={self.converged}, P={self.P!r})"
@@ -1171,6 +1151,23 @@ class EvidenceNotFinite(ValueError):
         self.total = float(total)
         super().__init__(f"the total log evidence is {total}: " + ("a trajectory has NaN windows, use nan='omit'"
                                                                    if np.isnan(total) else "a trajectory has no profile of positive weight"))
+
+
+def _fit_model(name, model):
+    """ the first refusal of `fit_markov_prior` and `fit_dwell_prior` (``name`` in the messages): TypeError unless a GenericGaussianModel """
+    from .gauss import GenericGaussianModel
+    if not isinstance(model, GenericGaussianModel):
+        raise TypeError(f"{name} needs a GenericGaussianModel, whose log-likelihood is a sum of segment terms, not "
+                        f"{type(model).__name__}")
+
+
+def _fit_trajs(name, trajs):
+    """ the trajectories of `fit_markov_prior` and `fit_dwell_prior`, at least one (ValueError) -> (single, items, n), n the frames of the longest """
+    single = not isinstance(trajs, (list, tuple))
+    items = [trajs] if single else list(trajs)
+    if not items:
+        raise ValueError(f"{name} needs at least one trajectory")
+    return single, items, max(len(t) for t in items)
 
 
 def _markov_start(model, start):
@@ -1214,27 +1211,19 @@ def fit_markov_prior(trajs, model, start=None, tol=1e-8, max_iter=200, nan='prop
 
     The total log evidence never decreases.  A state that the posterior never visits keeps its row.  Returns `MarkovPriorFit`.
     """
-    from .gauss import GenericGaussianModel
-    if not isinstance(model, GenericGaussianModel):
-        raise TypeError(f"fit_markov_prior needs a GenericGaussianModel, whose log-likelihood is a sum of segment terms, not "
-                        f"{type(model).__name__}")
+    _fit_model('fit_markov_prior', model)
     S = model.msd.shape[0]
     allowed, P, init = _markov_start(model, start)
     if not (tol > 0) or isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
         raise ValueError(f"tol = {tol!r} must be positive and max_iter = {max_iter!r} a positive integer")
-    single = not isinstance(trajs, (list, tuple))
-    items = [trajs] if single else list(trajs)
-    if not items:
-        raise ValueError("fit_markov_prior needs at least one trajectory")
-    n = max(len(t) for t in items)
+    single, items, n = _fit_trajs('fit_markov_prior', trajs)
     _check_exact_dwell(items, model, DwellPrior.markov(P, init, n=n), nan)
 
     ts = model.trajset(items[0] if single else items)       # built once: the iterations change the prior, not the tables
     history, converged = [], False
     for _ in range(int(max_iter)):
         prior = DwellPrior.markov(P, init, n=n)
-        res = _lib.gauss_dwell_evidence(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
-                                        marginals=True, omit=nan == 'omit')
+        res = _lib.gauss_dwell_evidence(model.handle(), ts, *prior.tables(), marginals=True, omit=nan == 'omit')
         total = float(np.sum(res['logev']))
         if not np.isfinite(total):
             raise EvidenceNotFinite(total)
@@ -1258,7 +1247,7 @@ def fit_markov_prior(trajs, model, start=None, tol=1e-8, max_iter=200, nan='prop
 
 # ---------------------------------------------------------------- gradient of the evidence under the dwell-time prior (section 23)
 
-class DwellSensitivities:
+class DwellSensitivities(_Record):
     """
     `exact_dwell_sensitivities` of n trajectories and P parameters:
 
@@ -1274,10 +1263,6 @@ class DwellSensitivities:
     """
 
     __slots__ = ('log_evidence', 'n_nan_windows', 'grad', 'expected_logL', 'fisher')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return f"DwellSensitivities(n={len(self.log_evidence)}, P={self.grad.shape[1]})"
@@ -1310,15 +1295,15 @@ def exact_dwell_sensitivities(trajs, model, prior, dmsd=None, dmsd_inf=None, dme
                                   expected_logL=np.zeros(0), fisher=np.zeros((0, P, P)) if fisher else None)
     arrs = model._direct_arrays(items)
     ts = model.trajset(items[0] if single else items)
-    res = _lib.gauss_dwell_sensitivities(model.handle(), ts, arrs, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
-                                         P=P, omit=nan == 'omit', fisher=fisher, scratch_bytes=scratch_bytes, **given)
+    res = _lib.gauss_dwell_sensitivities(model.handle(), ts, arrs, *prior.tables(), P=P, omit=nan == 'omit', fisher=fisher,
+                                         scratch_bytes=scratch_bytes, **given)
     return DwellSensitivities(log_evidence=res['logev'], n_nan_windows=res['n_nan_windows'], grad=res['grad'],
                               expected_logL=res['exp_logl'], fisher=res['fisher'])
 
 
 # ---------------------------------------------------------------- expected segment lengths and a fit of the dwell-time prior (section 24)
 
-class DwellLengthCounts:
+class DwellLengthCounts(_Record):
     """
     `exact_dwell_lengths` of one trajectory of T frames: the derivatives of `log_evidence` with respect to the prior's logs,
     which are posterior expected counts.
@@ -1335,10 +1320,6 @@ class DwellLengthCounts:
 
     __slots__ = ('traj', 'model', 'prior', 'nan', 'log_evidence', 'n_nan_windows', 'expected_jumps', 'expected_init',
                  'expected_dwell', 'expected_censored')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return f"DwellLengthCounts(T={len(self.traj)}, log_evidence={self.log_evidence!r}, n_nan_windows={self.n_nan_windows})"
@@ -1366,22 +1347,16 @@ def exact_dwell_lengths(trajs, model, prior, nan='propagate', scratch_bytes=0):
     of them.
     """
     single, items = _check_exact_dwell(trajs, model, prior, nan)
-    if not items:
-        return []
-    ts = model.trajset(items[0] if single else items)
-    res = _lib.gauss_dwell_lengths(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
-                                   omit=nan == 'omit', scratch_bytes=scratch_bytes)
-    out = [DwellLengthCounts(traj=t, model=model, prior=prior, nan=nan, log_evidence=float(res['logev'][j]),
-                             n_nan_windows=int(res['n_nan_windows'][j]), expected_jumps=res['exp_jumps'][j].copy(),
-                             expected_init=res['exp_init'][j].copy(), expected_dwell=res['exp_dwell'][j, :, :len(t)].copy(),
-                             expected_censored=res['exp_cens'][j, :, :len(t)].copy())
-           for j, t in enumerate(items)]
-    return out[0] if single else out
+    fields = lambda res, j, T: dict(n_nan_windows=int(res['n_nan_windows'][j]), expected_jumps=res['exp_jumps'][j].copy(),
+                                    expected_init=res['exp_init'][j].copy(), expected_dwell=res['exp_dwell'][j, :, :T].copy(),
+                                    expected_censored=res['exp_cens'][j, :, :T].copy())
+    return _dwell_per_trajectory(_lib.gauss_dwell_lengths, DwellLengthCounts, single, items, model, prior, nan, fields,
+                                 scratch_bytes=scratch_bytes)
 
 
 # ---------------------------------------------------------------- switch counts and first-contact times (section 27)
 
-class DwellSwitchCounts:
+class DwellSwitchCounts(_Record):
     """
     `exact_dwell_switch_counts` of one trajectory of T frames: the exact posterior of the number K of switches.
 
@@ -1396,10 +1371,6 @@ class DwellSwitchCounts:
     """
 
     __slots__ = ('traj', 'model', 'prior', 'nan', 'log_evidence', 'n_nan_windows', 'log_count', 'log_tail')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return (f"DwellSwitchCounts(T={len(self.traj)}, k_max={len(self.log_count) - 1}, log_evidence={self.log_evidence!r}, "
@@ -1453,19 +1424,13 @@ def exact_dwell_switch_counts(trajs, model, prior, k_max=None, nan='propagate', 
         k_max = top
     if isinstance(k_max, bool) or not isinstance(k_max, (int, np.integer)) or k_max < 0 or k_max > top:
         raise ValueError(f"k_max = {k_max!r}: an integer from 0 to {top}, the longest trajectory's T - 1, or None for that")
-    if not items:
-        return []
-    ts = model.trajset(items[0] if single else items)
-    res = _lib.gauss_dwell_switch_counts(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv, int(k_max),
-                                         omit=nan == 'omit', scratch_bytes=scratch_bytes)
-    out = [DwellSwitchCounts(traj=t, model=model, prior=prior, nan=nan, log_evidence=float(res['logev'][j]),
-                             n_nan_windows=int(res['n_nan_windows'][j]), log_count=res['log_count'][j].copy(),
-                             log_tail=float(res['log_tail'][j]))
-           for j, t in enumerate(items)]
-    return out[0] if single else out
+    fields = lambda res, j, T: dict(n_nan_windows=int(res['n_nan_windows'][j]), log_count=res['log_count'][j].copy(),
+                                    log_tail=float(res['log_tail'][j]))
+    return _dwell_per_trajectory(_lib.gauss_dwell_switch_counts, DwellSwitchCounts, single, items, model, prior, nan, fields, int(k_max),
+                                 scratch_bytes=scratch_bytes)
 
 
-class DwellFirstContact:
+class DwellFirstContact(_Record):
     """
     `exact_dwell_first_contact` of one trajectory of T frames: the exact posterior of the first frame in a target set of states.
 
@@ -1481,10 +1446,6 @@ class DwellFirstContact:
     """
 
     __slots__ = ('traj', 'model', 'prior', 'nan', 'target', 'log_evidence', 'n_nan_windows', 'log_first', 'log_never')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return (f"DwellFirstContact(T={len(self.traj)}, target={self.target}, log_evidence={self.log_evidence!r}, "
@@ -1528,21 +1489,15 @@ def exact_dwell_first_contact(trajs, model, prior, target, nan='propagate', scra
     """
     single, items = _check_exact_dwell(trajs, model, prior, nan)
     states = _target_states(target, model.msd.shape[0])
-    if not items:
-        return []
-    ts = model.trajset(items[0] if single else items)
-    res = _lib.gauss_dwell_first_contact(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
-                                         sum(1 << s for s in states), omit=nan == 'omit', scratch_bytes=scratch_bytes)
-    out = [DwellFirstContact(traj=t, model=model, prior=prior, nan=nan, target=states, log_evidence=float(res['logev'][j]),
-                             n_nan_windows=int(res['n_nan_windows'][j]), log_first=res['log_first'][j, :len(t)].copy(),
-                             log_never=float(res['log_never'][j]))
-           for j, t in enumerate(items)]
-    return out[0] if single else out
+    fields = lambda res, j, T: dict(target=states, n_nan_windows=int(res['n_nan_windows'][j]), log_first=res['log_first'][j, :T].copy(),
+                                    log_never=float(res['log_never'][j]))
+    return _dwell_per_trajectory(_lib.gauss_dwell_first_contact, DwellFirstContact, single, items, model, prior, nan, fields,
+                                 sum(1 << s for s in states), scratch_bytes=scratch_bytes)
 
 
 # ---------------------------------------------------------------- looped time (section 28)
 
-class DwellOccupancy:
+class DwellOccupancy(_Record):
     """
     `exact_dwell_occupancy` of one trajectory of T frames: the exact posterior of the number N of frames in a target set of
     states.  Every frame counts, observed or missing.
@@ -1558,10 +1513,6 @@ class DwellOccupancy:
     """
 
     __slots__ = ('traj', 'model', 'prior', 'nan', 'target', 'log_evidence', 'n_nan_windows', 'log_occupancy')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return (f"DwellOccupancy(T={len(self.log_occupancy) - 1}, target={self.target}, log_evidence={self.log_evidence!r}, "
@@ -1620,15 +1571,10 @@ def exact_dwell_occupancy(trajs, model, prior, target, nan='propagate', scratch_
     """
     single, items = _check_exact_dwell(trajs, model, prior, nan)
     states = _target_states(target, model.msd.shape[0])
-    if not items:
-        return []
-    ts = model.trajset(items[0] if single else items)
-    res = _lib.gauss_dwell_occupancy(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
-                                     sum(1 << s for s in states), omit=nan == 'omit', scratch_bytes=scratch_bytes)
-    out = [DwellOccupancy(traj=t, model=model, prior=prior, nan=nan, target=states, log_evidence=float(res['logev'][j]),
-                          n_nan_windows=int(res['n_nan_windows'][j]), log_occupancy=res['log_occ'][j, :len(t) + 1].copy())
-           for j, t in enumerate(items)]
-    return out[0] if single else out
+    fields = lambda res, j, T: dict(target=states, n_nan_windows=int(res['n_nan_windows'][j]),
+                                    log_occupancy=res['log_occ'][j, :T + 1].copy())
+    return _dwell_per_trajectory(_lib.gauss_dwell_occupancy, DwellOccupancy, single, items, model, prior, nan, fields,
+                                 sum(1 << s for s in states), scratch_bytes=scratch_bytes)
 
 
 def pooled_occupancy(results):
@@ -1709,7 +1655,7 @@ def hazard_m_step(dwell, cens, jumps, first, edges, hazard, jump, init, allowed=
     return hazard, jump, init, supported
 
 
-class DwellPriorFit:
+class DwellPriorFit(_Record):
     """
     `fit_dwell_prior`'s result.
 
@@ -1730,10 +1676,6 @@ class DwellPriorFit:
 
     __slots__ = ('edges', 'hazard', 'jump', 'init', 'log_evidence', 'n_iter', 'converged', 'expected_dwell', 'expected_censored',
                  'supported')
-
-    def __init__(self, **kw):
-        for name in self.__slots__:
-            setattr(self, name, kw[name])
 
     def __repr__(self):
         return f"DwellPriorFit(n_iter={self.n_iter}, converged={self.converged}, edges={self.edges.tolist()}, hazard={self.hazard!r})"
@@ -1805,15 +1747,8 @@ def fit_dwell_prior(trajs, model, edges=None, start=None, tol=1e-8, max_iter=500
     EM on a hidden semi-Markov model may stop at a local optimum.  No standard errors are reported: the expected counts are
     not observations, and the information of the marginal likelihood is not computed.  Returns `DwellPriorFit`.
     """
-    from .gauss import GenericGaussianModel
-    if not isinstance(model, GenericGaussianModel):
-        raise TypeError(f"fit_dwell_prior needs a GenericGaussianModel, whose log-likelihood is a sum of segment terms, not "
-                        f"{type(model).__name__}")
-    single = not isinstance(trajs, (list, tuple))
-    items = [trajs] if single else list(trajs)
-    if not items:
-        raise ValueError("fit_dwell_prior needs at least one trajectory")
-    n = max(len(t) for t in items)
+    _fit_model('fit_dwell_prior', model)
+    single, items, n = _fit_trajs('fit_dwell_prior', trajs)
     edges = _hazard_edges(edges, n)
     allowed, hazard, jump, init = _hazard_start(model, start, len(edges))
     if not (tol > 0) or isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1 or not (min_risk > 0):
@@ -1825,8 +1760,7 @@ def fit_dwell_prior(trajs, model, edges=None, start=None, tol=1e-8, max_iter=500
     history, converged = [], False
     for _ in range(int(max_iter)):
         prior = DwellPrior.from_hazard(hazard[:, bins], jump, init)
-        res = _lib.gauss_dwell_lengths(model.handle(), ts, prior.log_init, prior.log_jump, prior.log_dwell, prior.log_surv,
-                                       omit=nan == 'omit')
+        res = _lib.gauss_dwell_lengths(model.handle(), ts, *prior.tables(), omit=nan == 'omit')
         total = float(np.sum(res['logev']))
         if not np.isfinite(total):
             raise EvidenceNotFinite(total)
