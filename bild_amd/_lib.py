@@ -199,6 +199,14 @@ _SIGNATURES = {
     'bild_choice_counts': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
 }
 
+# the calls of include/bild_amd_windows.h: bound by `lib()` as the table above is, and no part of `exported_symbols()`, which
+# lists include/bild_amd.h
+_SIGNATURES_EXT = {
+    # exact window support under a dwell-time prior (gauss_dwellwin.cpp)
+    'bild_gauss_dwell_windows': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                _ip, _ip, _ip, _ip, ctypes.c_uint, _vp]),
+}
+
 _lib = None
 _torch_libdir = None     # set when the library was bound to the HIP runtime of an installed PyTorch
 _rccl_chosen = False
@@ -240,7 +248,7 @@ def lib():
                               f"or `make -C bild_amd/csrc` (there is no CPU fallback)")
         _share_hip_runtime_with_torch()
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _SIGNATURES.items():
+        for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_EXT}.items():
             fn = getattr(handle, name)
             fn.restype = restype
             fn.argtypes = argtypes
@@ -1526,6 +1534,31 @@ def gauss_dwell_occupancy(model, ts, log_init, log_jump, log_dwell, log_surv, ta
         'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_occ': np.empty((n, T_max + 1, S))}
     return _dwell_call('bild_gauss_dwell_occupancy', DwellOccupancyOut, model, ts, (log_init, log_jump, log_dwell, log_surv), outputs,
                        scalars=(target,), omit=omit, scratch_bytes=scratch_bytes)
+
+
+class DwellWindowsOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'log_all', 'n_nan_windows')]
+
+
+def gauss_dwell_windows(model, ts, log_init, log_jump, log_dwell, log_surv, win_traj, win_u, win_v, win_target, omit=False,
+                        scratch_bytes=0):
+    """
+    exact window support under a dwell-time prior (bild_gauss_dwell_windows, include/bild_amd_windows.h): query i asks for
+    log P(every frame of [win_u[i], win_v[i]) is in the states of the bit mask win_target[i] | data) on trajectory win_traj[i] of
+    the set, win_traj not decreasing.  A dict of logev (n_traj,), log_all (n_win,) and n_nan_windows (n_traj,) int64
+    """
+    (log_init, log_jump, log_dwell, log_surv), L = _dwell_tables(model, log_init, log_jump, log_dwell, log_surv)
+    win_traj, win_u, win_v = i32(win_traj), i32(win_u), i32(win_v)
+    win_target = np.ascontiguousarray(win_target, dtype=np.uint32)
+    n = len(win_traj)
+    assert win_traj.shape == win_u.shape == win_v.shape == win_target.shape == (n,)
+    T_max = int(np.max(ts.T))
+    res = {'logev': np.empty(ts.n_traj), 'log_all': np.empty(n), 'n_nan_windows': np.empty(ts.n_traj, dtype=np.int64)}
+    spec = _out(DwellWindowsOut, res)
+    check(lib().bild_gauss_dwell_windows(model._h, ts._h, L, dptr(log_init), dptr(log_jump), dptr(log_dwell), dptr(log_surv), T_max,
+                                         int(scratch_bytes), n, iptr(win_traj), iptr(win_u), iptr(win_v), aptr(win_target),
+                                         DWELL_NAN_OMIT if omit else DWELL_NAN_PROPAGATE, ctypes.byref(spec)))
+    return res
 
 
 class DwellFilterOut(ctypes.Structure):

@@ -138,6 +138,10 @@ int launch_dwell_contact(const DwellParams &, const DwellContact &, void *) { re
 namespace bild {
 int launch_dwell_occupancy(const DwellParams &, const DwellOccupancy &, int, void *) { return 1; }
 }
+#include "gauss_dwellwin.h"
+namespace bild {
+int launch_dwell_windows(const DwellParams &, const DwellWindows &, void *) { return 1; }
+}
 #include "gauss_dwelldraw.h"
 namespace bild {
 int launch_dwelldraw_head(const DwelldrawParams &, void *) { return 1; }

@@ -42,6 +42,10 @@ frame in a set of states together with the probability that there is none.
 
 `exact_dwell_occupancy` (bild_gauss_dwell_occupancy) is the exact posterior of a third: the number of
 frames spent in a set of states, the looped fraction of the trajectory; `pooled_occupancy` is that of a whole data set.
+
+`exact_dwell_windows` (bild_gauss_dwell_windows) is the exact posterior probability that every frame of a
+window is in a set of states, for any number of windows a trajectory; `ExactDwellResults.map_support` asks it about the MAP
+profile: how well the posterior supports each called segment and the placement of each called switch.
 """
 import math
 import warnings
@@ -753,6 +757,41 @@ class ExactDwellResults(_Record):
         mean, var = self.model.kalman_mixture(draws.segments(), [self.traj], np.zeros(len(draws)))
         return mean[0], var[0]
 
+    def map_support(self, radii=(0, 2, 5), scratch_bytes=0):
+        """
+        How well the exact posterior supports the MAP profile, as `DwellMapSupport`, from ONE `exact_dwell_windows` call: per
+        called segment the probability that every frame of it is in its state and that none is, and per called switch frame c
+        and radius r of ``radii`` (non-negative integers) the probability of at least one switch at the frames c - r ... c + r.
+        ValueError without a MAP profile, for a model of one state, and for a radius that is not a non-negative integer.
+        """
+        S = self.model.msd.shape[0]
+        if self.map_profile is None:
+            raise ValueError("the results have no MAP profile to support")
+        if S < 2:
+            raise ValueError("a model of one state has no other profile: nothing to support")
+        radii = tuple(radii)
+        if any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < 0 for r in radii):
+            raise ValueError(f"radii = {radii!r}: non-negative integers")
+        states = np.asarray(self.map_profile[:], dtype=int)
+        T = len(states)
+        starts = np.concatenate(([0], np.flatnonzero(np.diff(states) != 0) + 1))
+        ends = np.append(starts[1:], T)
+        seg_state = states[starts]
+        windows = []
+        for a, b, s in zip(starts, ends, seg_state):
+            windows.append((int(a), int(b), (int(s),)))
+            windows.append((int(a), int(b), tuple(r for r in range(S) if r != s)))
+        for c in starts[1:]:
+            for r in radii:
+                windows.extend((max(int(c) - int(r) - 1, 0), min(int(c) + int(r) + 1, T), (s,)) for s in range(S))
+        res = exact_dwell_windows(self.traj, self.model, self.prior, windows, nan=self.nan, scratch_bytes=scratch_bytes)
+        n_seg = len(starts)
+        same = np.exp(res.log_all[2 * n_seg:]).reshape(n_seg - 1, len(radii), S)
+        return DwellMapSupport(traj=self.traj, model=self.model, prior=self.prior, nan=self.nan, radii=radii, seg_start=starts, seg_end=ends,
+                               seg_state=seg_state, log_whole=res.log_all[0:2 * n_seg:2].copy(), log_absent=res.log_all[1:2 * n_seg:2].copy(),
+                               switch_frames=starts[1:].copy(), p_switch_within=1.0 - same.sum(axis=2), n_queries=len(windows),
+                               log_evidence=res.log_evidence, n_nan_windows=res.n_nan_windows)
+
 
 def _check_exact_dwell(trajs, model, prior, nan):
     """ every refusal of `exact_dwell`; returns (single, items) """
@@ -1050,6 +1089,19 @@ class ExactDwellDraws:
         """
         wanted = [target] if isinstance(target, (int, np.integer)) else list(target)
         return np.isin(self._states[:, :self.T], np.asarray(wanted, dtype=np.int64)).sum(axis=1).astype(np.int64)
+
+    def all_in(self, u, v, target):
+        """
+        the fraction of the draws with every frame of [u, v), 0 <= u < v <= T, in ``target`` or, for a collection, in one of its
+        states (host only; NaN without draws).  The counting counterpart of `exact_dwell_windows`, with the standard error
+        sqrt(p (1 - p) / n) of a count.
+        """
+        if not 0 <= u < v <= self.T:
+            raise ValueError(f"window [{u}, {v}): 0 <= u < v <= T = {self.T} expected")
+        wanted = [target] if isinstance(target, (int, np.integer)) else list(target)
+        if len(self) == 0:
+            return float('nan')
+        return float(np.isin(self._states[:, u:v], np.asarray(wanted, dtype=np.int64)).all(axis=1).mean())
 
 
 def exact_dwell_draw(results, n, seed=0, uniforms=None, keep_uniforms=0, scratch_bytes=0):
@@ -1595,6 +1647,126 @@ def pooled_occupancy(results):
             raise ValueError(f"result {j} is NaN (n_nan_windows = {r.n_nan_windows}, log_evidence = {r.log_evidence!r})")
         total = np.convolve(total, pmf)
     return total
+
+
+# ---------------------------------------------------------------- windows and called segments (section 29)
+
+class DwellWindowSupport(_Record):
+    """
+    `exact_dwell_windows` of one trajectory of T frames: for each of its n windows the exact posterior probability that every
+    frame of the window is in the window's set of states.
+
+    traj, model, prior, nan : as given
+    windows : (n, 2) int array, the windows [u, v); targets : their sets of states, a tuple of sorted tuples
+    log_evidence, n_nan_windows : `exact_dwell`'s numbers, bit for bit
+    log_all : (n,) log P(theta_t in the set for every u <= t < v | data); -inf where the probability is 0
+
+    Normalised by `log_evidence`.  Under nan='propagate' a trajectory with `n_nan_windows` > 0 is NaN in all but
+    `n_nan_windows`; a trajectory without a profile of positive weight has `log_evidence` -inf and NaN in `log_all`.
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'windows', 'targets', 'log_evidence', 'n_nan_windows', 'log_all')
+
+    def __repr__(self):
+        return f"DwellWindowSupport(T={len(self.traj)}, windows={len(self.log_all)}, log_evidence={self.log_evidence!r})"
+
+    def p_all(self):
+        """ (n,) P(every frame of the window is in its set | data) """
+        return np.exp(self.log_all)
+
+    def p_not_all(self):
+        """
+        (n,) P(some frame of the window is outside its set | data) = -expm1(`log_all`).  Its absolute error is that of
+        `log_all`, so its relative error grows as it nears 0: a window that the posterior supports at 1 - 1e-12 has few
+        correct digits here.
+        """
+        return -np.expm1(self.log_all)
+
+
+def _window_queries(windows, S, T, where):
+    """ one trajectory's windows (u, v, target) -> ((n, 2) int array, tuple of sorted state tuples); ValueError on a bad one """
+    try:
+        rows = [tuple(w) for w in windows]
+    except TypeError:
+        raise ValueError(f"the windows{where}: a sequence of (u, v, target)") from None
+    uv, targets = np.zeros((len(rows), 2), dtype=np.int64), []
+    for i, w in enumerate(rows):
+        if len(w) != 3:
+            raise ValueError(f"window {i}{where} = {w!r}: (u, v, target) expected")
+        u, v, target = w
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in (u, v)) or not 0 <= u < v <= T:
+            raise ValueError(f"window {i}{where} = [{u!r}, {v!r}): integers with 0 <= u < v <= T = {T} expected")
+        uv[i] = u, v
+        targets.append(_target_states(target, S))
+    return uv, tuple(targets)
+
+
+def exact_dwell_windows(trajs, model, prior, windows, nan='propagate', scratch_bytes=0):
+    """
+    The exact posterior probability, under a dwell-time prior, that a `GenericGaussianModel` profile is in the states `target`
+    at EVERY frame of a window [u, v), for any number of windows a trajectory: "is this called loop really there?".  The
+    forward recursion of `exact_dwell` restricted to the target over the window, started from the unconstrained forward
+    tables at its left edge and closed with the backward tables at its right edge; the windows of a call run in parallel on the
+    GPU (bild_gauss_dwell_windows).  The per-frame marginals cannot give this number: they lose the
+    correlation between frames.  The probability that SOME frame of the window is in a set is `p_not_all` of its complement.
+
+    trajs, model, prior, nan, scratch_bytes : as for `exact_dwell`; a list gives a list of results from ONE device call
+    windows : a sequence of (u, v, target), 0 <= u < v <= T, for one trajectory; for a list of trajectories a list of such
+        sequences, one a trajectory (an empty one: that trajectory still gets its evidence).  A target is a state or a
+        collection of states, a non-empty proper subset of the model's (so a model of one state has no valid window).
+
+    Every refusal is `exact_dwell`'s, the target's, a window outside its trajectory or a list of the wrong length (ValueError)
+    and is raised before the trajectories are uploaded.  Returns `DwellWindowSupport` or a list of them.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    S = model.msd.shape[0]
+    try:
+        per_traj = [windows] if single else list(windows)
+    except TypeError:
+        raise ValueError("windows: a list of sequences of (u, v, target), one a trajectory") from None
+    if len(per_traj) != len(items):
+        raise ValueError(f"{len(per_traj)} sequences of windows for {len(items)} trajectories")
+    parsed = [_window_queries(w, S, len(t), '' if single else f" of trajectory {j}") for j, (w, t) in enumerate(zip(per_traj, items))]
+    counts = np.array([len(uv) for uv, _ in parsed], dtype=np.int64)
+    first = np.concatenate(([0], np.cumsum(counts)))
+    uv = np.concatenate([uv for uv, _ in parsed] + [np.zeros((0, 2), dtype=np.int64)])
+    masks = np.array([sum(1 << s for s in g) for _, targets in parsed for g in targets], dtype=np.uint32)
+
+    def fields(res, j, T):
+        return dict(windows=parsed[j][0], targets=parsed[j][1], n_nan_windows=int(res['n_nan_windows'][j]),
+                    log_all=res['log_all'][first[j]:first[j + 1]].copy())
+    return _dwell_per_trajectory(_lib.gauss_dwell_windows, DwellWindowSupport, single, items, model, prior, nan, fields,
+                                 np.repeat(np.arange(len(items)), counts), uv[:, 0], uv[:, 1], masks, scratch_bytes=scratch_bytes)
+
+
+class DwellMapSupport(_Record):
+    """
+    `ExactDwellResults.map_support`: the exact posterior's support of the MAP profile of one trajectory of T frames, the
+    confidence column of a called profile.
+
+    traj, model, prior, nan : those of the results; log_evidence, n_nan_windows : `exact_dwell`'s numbers
+    seg_start, seg_end, seg_state : (n_seg,) the called segments [start, end) and their states
+    log_whole : (n_seg,) log P(every frame of the segment is in its state | data)
+    log_absent : (n_seg,) log P(no frame of the segment is in its state | data)
+    radii : as given; switch_frames : (n_seg - 1,) the called switch frames c (the first frame of the new state)
+    p_switch_within : (n_seg - 1, len(radii)) P(at least one switch at the frames c - r ... c + r | data), the range clamped to
+        the trajectory: 1 - sum_s P(the frames max(c - r - 1, 0) ... min(c + r, T - 1) are all in s)
+    n_queries : the windows of the one device call
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'radii', 'seg_start', 'seg_end', 'seg_state', 'log_whole', 'log_absent',
+                 'switch_frames', 'p_switch_within', 'n_queries', 'log_evidence', 'n_nan_windows')
+
+    def __repr__(self):
+        return f"DwellMapSupport(T={len(self.traj)}, segments={len(self.seg_start)}, radii={self.radii}, n_queries={self.n_queries})"
+
+    def p_whole(self):
+        """ (n_seg,) P(every frame of the segment is in its state | data) """
+        return np.exp(self.log_whole)
+
+    def p_present(self):
+        """ (n_seg,) P(some frame of the segment is in its state | data) = -expm1(`log_absent`) """
+        return -np.expm1(self.log_absent)
 
 
 def _hazard_edges(edges, n):
