@@ -9,10 +9,11 @@ import time
 
 import numpy as np
 
+import dwell_cases as DC
 import dwell_event_cases as DEC
 import dwell_window_oracle as DW
 
-TARGETS = {2: ((1,), (0,)), 3: ((1,), (0, 2))}
+TARGETS = {2: ((1,), (0,)), 3: ((1,), (0, 2)), 4: ((0,), (1, 3), (0, 1, 2))}
 MAX_WINDOWS = 16
 
 # (S, T, missing frames, prior kind, nan mode): T around the 64-frame tiles of the window chain; S = 3 (the jump 0 -> 2
@@ -63,6 +64,68 @@ def case_id(case):
 def case_windows(case):
     S, T, part = case[0], case[1], case[5]
     return windows_of(S, T)[part * MAX_WINDOWS:(part + 1) * MAX_WINDOWS]
+
+
+def wide_spans(T):
+    """
+    `spans(T)` and, from T = 257 on: chains whose head alpha(c <= u) lies in tile 3 or 4 and whose closure has the one end
+    frame T, (192, T), (255, T) and (256, T); a chain of 64 frames that ends one frame before T, so that the closure has two end
+    frames; and (191, 257), (192, 258), clipped to the trajectory: closures with 65 and 64 end frames at T = 321.  (0, T), a
+    chain of five or six tiles, is `spans`' own
+    """
+    out = spans(T)
+    if T >= 257:
+        for u, v in ((0, T), (192, T), (255, T), (256, T), (T - 66, T - 1), (191, min(257, T)), (192, min(258, T))):
+            if 0 <= u < v <= T and (u, v) not in out:
+                out.append((u, v))
+    return out
+
+
+def wide_windows_of(case):
+    """ every span of `wide_spans` with every target of the case's S, as (u, v, target) """
+    return [(u, v, target) for u, v in wide_spans(case[1]) for target in DEC.WIDE_TARGETS[case[0]]]
+
+
+# (case, part): the wide cases of `dwell_event_cases.WIDE` that have a proper subset, their windows in parts of MAX_WINDOWS
+WIDE_CASES = [(case, part) for case in DEC.WIDE if case[0] > 1 for part in range(-(-len(wide_windows_of(case)) // MAX_WINDOWS))]
+
+
+def wide_id(item):
+    case, part = item
+    return DEC.wide_id(case) + f"_part{part}"
+
+
+def wide_windows(item):
+    case, part = item
+    return wide_windows_of(case)[part * MAX_WINDOWS:(part + 1) * MAX_WINDOWS]
+
+
+def _solve(key, W, F, prior, windows):
+    start = time.perf_counter()
+    out = DW.solve(W, F, prior, windows)
+    ORACLE_SECONDS[key] = time.perf_counter() - start
+    for a in out.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def wide_answer(item):
+    """ `dwell_window_oracle.solve` of an entry of WIDE_CASES on its windows """
+    _, _, prior, W, F = DC.oracle_case(item[0])
+    return _solve(item, W, F, prior, wide_windows(item))
+
+
+def ragged_windows(T):
+    """ the windows of a trajectory of `dwell_cases.ragged_case`: `spans(T)`, which keeps what fits, with both ragged targets """
+    return [(u, v, target) for u, v in spans(T) for target in DEC.RAGGED_TARGETS]
+
+
+@functools.lru_cache(maxsize=None)
+def ragged_answer(j):
+    _, prior, xs, tabs = DC.ragged_case()
+    return _solve(('ragged', j), *tabs[j], prior, ragged_windows(len(xs[j])))
 
 
 @functools.lru_cache(maxsize=None)

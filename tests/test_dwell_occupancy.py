@@ -10,7 +10,9 @@ import pytest
 
 import bild_amd
 import dwell_cases as DC
+import dwell_event_cases as DEC
 import dwell_event_oracle as DE
+import dwell_occupancy_cases as DQC
 import dwell_occupancy_oracle as DQ
 import dwell_oracle as DO
 import segment_cases as C
@@ -76,6 +78,28 @@ def test_oracle_against_enumeration_and_identities(name, kind):
         worst = close_logs(got['log_occupancy'], want['log_occupancy'], (name, kind, target))
         print(f"{target}: worst deviation of a log from the enumeration {worst:.1e}")
         identities(W, F, prior, target, model, x)
+
+
+@pytest.mark.parametrize('name', [n for n in DEC.SMALL if DEC.SMALL[n][0] > 1])
+def test_oracle_against_enumeration_at_four_states_and_hard_priors(name):
+    """ the oracle is the statement at these shapes too: `dwell_event_cases.SMALL`, every target of S, one frame missing """
+    S, T, gap, kind = DEC.SMALL[name]
+    model, x, prior, W, F = DEC.small_case(name)
+    assert model.nStates == prior.nStates == S and np.array_equal(np.flatnonzero(np.isnan(x[:, 0])), [gap]) and F.shape == (S, T + 1)
+    n_inf = 0
+    for target in DEC.SMALL_TARGETS[S]:
+        got, want = DQ.solve(W, F, prior, target), DQ.enumerate_all(W, F, prior, target)
+        assert got['n_nan_windows'] == 0 and want['n_nan'] == 0 and got['log_occupancy'].shape == (T + 1, S)
+        assert np.isfinite(want['logev']) and abs(got['logev'] - want['logev']) < TOL
+        worst = close_logs(got['log_occupancy'], want['log_occupancy'], (name, target))
+        print(f"{target}: worst deviation of a log from the enumeration {worst:.1e}")
+        identities(W, F, prior, target, model, x)
+        assert np.array_equal(got['log_occupancy'] > -np.inf, DQ.prior_support(prior, target, S, T)), target
+        n_inf += int(np.sum(got['log_occupancy'] == -np.inf))
+    print(f"{name}: {n_inf} entries at -inf")
+    assert n_inf > 0        # (n = 0 and n = T end in one state set alone, under every prior)
+    if kind == 'flip':      # the states alternate: T / 2 frames in either, T even
+        assert T % 2 == 0 and np.all(np.isfinite(got['log_occupancy'][T // 2])) and np.all(np.delete(got['log_occupancy'], T // 2, axis=0) == -np.inf)
 
 
 @pytest.mark.parametrize('kind', ['markov', 'nongeometric', 'minlength'])
@@ -214,3 +238,60 @@ def test_refusals_come_before_any_upload(monkeypatch):
     assert call([], model, prior, 1) == []
     with pytest.raises(ValueError):
         call([], model, prior, 2)
+
+
+# ---------------------------------------------------------------- the conditions on the inputs of the wide GPU cases
+
+# per wide case and target, in the order of `dwell_event_cases.WIDE_TARGETS`, the finite entries of log_occupancy that the oracle
+# gives, of (T + 1) S.  Listed, so that a change of a generator that empties a comparison is seen here.
+WIDE_FINITE = {
+    (4, 64, (), 'minlength'): (252, 252, 252), (4, 129, (64, 100), 'markov'): (516, 516, 516),
+    (4, 257, (100,), 'nongeometric'): (1028, 1028, 1028), (2, 256, (), 'markov'): (512, 512), (2, 257, (255,), 'minlength'): (512, 512),
+    (3, 321, (128,), 'markov'): (963, 963, 963), (2, 65, (), 'nongeometric'): (130, 130), (3, 193, (3,), 'nongeometric'): (579, 579, 579),
+    (2, 130, (), 'bounded'): (256, 256), (3, 193, (), 'bounded'): (573, 570, 570), (2, 65, (), 'one_start'): (128, 128),
+    (3, 130, (20,), 'absorbing'): (132, 390, 390), (2, 70, (), 'flip'): (2, 2),
+}
+
+
+@pytest.mark.parametrize('case', [c for c in DEC.WIDE if c[0] > 1], ids=DEC.wide_id)
+def test_gpu_wide_cases_meet_their_conditions(case):
+    """ what tests/test_gpu_dwell_occupancy.py compares the device with is what it is meant to be, and no comparison is vacuous """
+    S, T, missing, kind = case
+    model, x, prior, W, F = DC.oracle_case(case)
+    assert model.nStates == prior.nStates == S and x.shape == (T, 2) and prior.L == T + 5
+    assert np.array_equal(np.flatnonzero(np.isnan(x[:, 0])), missing)
+    targets = DEC.WIDE_TARGETS[S]
+    assert [item for item in DQC.WIDE_CASES if item[0] == case] == [(case, target) for target in targets]
+    assert len(WIDE_FINITE[case]) == len(targets)
+    for target, finite in zip(targets, WIDE_FINITE[case]):
+        want = DQC.wide_answer(case, target)
+        occ = want['log_occupancy']
+        assert want['n_nan_windows'] == 0 and np.isfinite(want['logev']) and occ.shape == (T + 1, S) and not np.any(np.isnan(occ))
+        assert abs(np.exp(occ).sum() - 1) < 1e-10
+        print(f"{case} {target}: oracle {DQC.ORACLE_SECONDS[case, target]:.1f} s, {finite} of {(T + 1) * S} entries finite")
+        assert DQC.ORACLE_SECONDS[case, target] < 20
+        # n = 0 ends outside the target and n = T inside it, so every case compares entries at -inf as well as finite ones;
+        # the hard priors empty more than those 2 S rows' worth
+        assert 0 < int(np.sum(occ > -np.inf)) == finite <= (T + 1) * S - S
+    if kind in DEC.HARD:    # (under some target; 'absorbing' under (2,))
+        assert min(WIDE_FINITE[case]) < (T + 1) * S - S
+    if kind == 'absorbing':     # state 2 is never left: n frames in it, ending elsewhere, is n = 0 alone
+        assert np.all(DQC.wide_answer(case, (2,))['log_occupancy'][1:, :2] == -np.inf)
+    if kind == 'flip':
+        assert np.all(np.isfinite(DQC.wide_answer(case, (1,))['log_occupancy'][T // 2])) and T % 2 == 0
+
+
+def test_gpu_ragged_batch_meets_its_conditions():
+    _, _, xs, _ = DC.ragged_case()
+    for j, x in enumerate(xs):
+        T = len(x)
+        for target in DEC.RAGGED_TARGETS:
+            want = DQC.ragged_answer(j, target)
+            occ = want['log_occupancy']
+            assert want['n_nan_windows'] == 0 and np.isfinite(want['logev']) and occ.shape == (T + 1, 4) and not np.any(np.isnan(occ))
+            # non-geometric tables exclude nothing: -inf is n = 0 ending in the target, n = T ending outside it, and nothing else
+            inside = np.isin(np.arange(4), target)
+            empty = np.zeros((T + 1, 4), dtype=bool)
+            empty[0, inside] = empty[T, ~inside] = True
+            assert np.array_equal(occ == -np.inf, empty)
+            assert DQC.ORACLE_SECONDS['ragged', j, target] < 20

@@ -16,9 +16,11 @@ import pytest
 
 import bild_amd
 import dwell_cases as DC
+import dwell_event_cases as DEC
 import dwell_event_oracle as DE
 import dwell_occupancy_oracle as DQ
 import dwell_oracle as DO
+import dwell_window_cases as DWC
 import dwell_window_oracle as DW
 import segment_cases as C
 import test_abi_header as AH
@@ -78,6 +80,33 @@ def test_oracle_against_enumeration(name, kind):
         assert got['n_nan_windows'] == 0 and abs(got['logev'] - want['logev']) < TOL
         worst = close_logs(got['log_all'], want['log_all'], (name, kind, solve.__name__))
         print(f"{solve.__name__}: worst deviation of a log from the enumeration {worst:.1e}")
+
+
+@pytest.mark.parametrize('name', [n for n in DEC.SMALL if DEC.SMALL[n][0] > 1])
+def test_oracle_against_enumeration_at_four_states_and_hard_priors(name):
+    """ both formulations are the statement at these shapes too: `dwell_event_cases.SMALL`, every (u, v) with every target of S """
+    S, T, gap, kind = DEC.SMALL[name]
+    model, x, prior, W, F = DEC.small_case(name)
+    assert model.nStates == prior.nStates == S and np.array_equal(np.flatnonzero(np.isnan(x[:, 0])), [gap]) and F.shape == (S, T + 1)
+    windows = [(u, v, target) for target in DEC.SMALL_TARGETS[S] for u in range(T) for v in range(u + 1, T + 1)]
+    want = DW.enumerate_all(W, F, prior, windows)
+    assert want['n_nan'] == 0 and np.isfinite(want['logev'])
+    for solve in (DW.solve, DW.solve_masked):
+        got = solve(W, F, prior, windows)
+        assert got['n_nan_windows'] == 0 and abs(got['logev'] - want['logev']) < TOL
+        worst = close_logs(got['log_all'], want['log_all'], (name, solve.__name__))
+        print(f"{solve.__name__}: {len(windows)} windows, {int(np.sum(got['log_all'] == -np.inf))} at -inf, worst deviation of a log from the enumeration {worst:.1e}")
+    empty = {w for w, v in zip(windows, want['log_all']) if v == -np.inf}
+    if kind in ('nongeometric', 'minlength'):
+        assert not empty
+    if kind == 'flip':          # the states alternate: one frame alone stays in one state
+        assert empty == {w for w in windows if w[1] - w[0] > 1}
+    if kind == 'bounded3':      # no segment longer than 3 frames
+        assert empty == {w for w in windows if w[1] - w[0] > 3}
+    if kind == 'one_start':     # every profile starts in state 2
+        assert empty == {w for w in windows if w[0] == 0 and 2 not in w[2]}
+    if kind == 'absorbing':     # state 2 is never left, and 0 -> 2 is forbidden: nothing is excluded outright but a return
+        assert not empty and np.all(prior.log_jump[2] == -np.inf)
 
 
 @pytest.mark.parametrize('kind', ['markov', 'nongeometric', 'minlength'])
@@ -296,6 +325,75 @@ def test_refusals_come_before_any_upload(monkeypatch):
     assert call([], model, prior, []) == []
     with pytest.raises(ValueError):
         call([], model, prior, [good])
+
+
+# ---------------------------------------------------------------- the conditions on the inputs of the wide GPU cases
+
+# per wide case what the oracle gives over all parts: (finite windows, windows at -inf).  Listed, so that a change of a
+# generator that empties a comparison is seen here.
+WIDE_FINITE = {
+    (4, 64, (), 'minlength'): (21, 0), (4, 129, (64, 100), 'markov'): (54, 0), (4, 257, (100,), 'nongeometric'): (75, 0),
+    (2, 256, (), 'markov'): (42, 0), (2, 257, (255,), 'minlength'): (50, 0), (3, 321, (128,), 'markov'): (81, 0),
+    (2, 65, (), 'nongeometric'): (18, 0), (3, 193, (3,), 'nongeometric'): (63, 0), (2, 130, (), 'bounded'): (36, 2),
+    (3, 193, (), 'bounded'): (56, 7), (2, 65, (), 'one_start'): (15, 3), (3, 130, (20,), 'absorbing'): (57, 0), (2, 70, (), 'flip'): (8, 18),
+}
+
+
+@pytest.mark.parametrize('case', [c for c in DEC.WIDE if c[0] > 1], ids=DEC.wide_id)
+def test_gpu_wide_cases_meet_their_conditions(case):
+    """ what tests/test_gpu_dwell_windows.py compares the device with is what it is meant to be, and no comparison is vacuous """
+    S, T, missing, kind = case
+    model, x, prior, W, F = DC.oracle_case(case)
+    assert model.nStates == prior.nStates == S and x.shape == (T, 2) and prior.L == T + 5
+    assert np.array_equal(np.flatnonzero(np.isnan(x[:, 0])), missing)
+    spans = DWC.wide_spans(T)
+    assert spans[:len(DWC.spans(T))] == DWC.spans(T) and len(set(spans)) == len(spans) and all(0 <= u < v <= T for u, v in spans)
+    if T >= 257:
+        assert {(0, T), (192, T), (255, T), (256, T), (T - 66, T - 1), (191, 257), (192, min(258, T))} <= set(spans)
+        assert max(v - u - 1 for u, v in spans) // 64 + 1 == -(-T // 64)         # a chain of as many tiles as the trajectory has
+    items = [item for item in DWC.WIDE_CASES if item[0] == case]
+    windows = [w for item in items for w in DWC.wide_windows(item)]
+    assert windows == [(u, v, target) for u, v in spans for target in DEC.WIDE_TARGETS[S]] and [item[1] for item in items] == list(range(len(items)))
+    values = np.concatenate([DWC.wide_answer(item)['log_all'] for item in items])
+    for item in items:
+        want = DWC.wide_answer(item)
+        assert want['n_nan_windows'] == 0 and np.isfinite(want['logev']) and DWC.ORACLE_SECONDS[item] < 20
+    assert values.shape == (len(windows),) and not np.any(np.isnan(values)) and np.all(values <= 1e-12)
+    print(f"{case}: {len(items)} parts, {len(windows)} windows, {int(np.sum(values == -np.inf))} at -inf, slowest part "
+          f"{max(DWC.ORACLE_SECONDS[item] for item in items):.2f} s")
+    assert (int(np.sum(values > -np.inf)), int(np.sum(values == -np.inf))) == WIDE_FINITE[case] and WIDE_FINITE[case][0] > 0
+    empty = {w for w, v in zip(windows, values) if v == -np.inf}
+    if kind in ('bounded', 'one_start', 'flip'):    # the oracle decides which windows are -inf, and there are some
+        assert empty
+    if kind == 'flip':      # every window of two or more frames: the case keeps its one-frame windows
+        assert empty == {w for w in windows if w[1] - w[0] > 1} and any(w[1] - w[0] == 1 for w in windows)
+    if kind == 'one_start':
+        assert empty == {w for w in windows if w[0] == 0 and S - 1 not in w[2]}
+    if kind == 'bounded':   # a window in one state longer than the bound
+        assert {w for w in windows if len(w[2]) == 1 and w[1] - w[0] > DC.BOUND} <= empty
+    if case == (2, 130, (), 'bounded'):
+        more = [(0, 130, (1,)), (0, 129, (1,)), (1, 130, (1,)), (3, 129, (1,)), (63, 128, (1,))]
+        got = DW.solve(W, F, prior, more)['log_all']
+        assert np.all(got[:4] == -np.inf) and np.isfinite(got[4]) and (63, 128, (1,)) in windows and (0, 130, (1,)) in empty
+
+
+def test_gpu_ragged_batch_meets_its_conditions():
+    _, _, xs, _ = DC.ragged_case()
+    counts = []
+    for j, x in enumerate(xs):
+        T = len(x)
+        windows, want = DWC.ragged_windows(T), DWC.ragged_answer(j)
+        assert all(0 <= u < v <= T and target in DEC.RAGGED_TARGETS for u, v, target in windows)
+        assert want['n_nan_windows'] == 0 and np.isfinite(want['logev']) and np.all(np.isfinite(want['log_all'])) and len(want['log_all']) == len(windows)
+        assert DWC.ORACLE_SECONDS['ragged', j] < 20
+        counts.append(len(windows))
+    assert counts == [2, 42, 14, 38, 6, 18]       # T = 1 and T = 2 get only what fits
+
+
+def test_gpu_wide_siblings_are_wide_cases():
+    import test_gpu_dwell_windows as GW
+    assert all(len(t) == 1 and t[0] in DEC.WIDE and t[0][0] == 4 for t in GW.WIDE_SIBLINGS) and 4 in DWC.TARGETS
+    assert DWC.TARGETS[4] == DEC.WIDE_TARGETS[4] and set(DWC.TARGETS[2]) == set(DEC.WIDE_TARGETS[2]) and set(DWC.TARGETS[3]) < set(DEC.WIDE_TARGETS[3])
 
 
 # ---------------------------------------------------------------- the binding against include/bild_amd_windows.h

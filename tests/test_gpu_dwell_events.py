@@ -68,6 +68,57 @@ def test_against_oracle(case):
         assert np.all(r.log_count[1:] == -np.inf) and abs(np.log(r.pmf()[0])) < TOL_LOG
 
 
+def hold_counts(r, want, ref, S, T, k_max, what):
+    """ a `DwellSwitchCounts` against the oracle's answer and `exact_dwell`'s evidence: {name: deviation}, the bars asserted """
+    rows = T if k_max is None else k_max + 1
+    assert r.log_count.shape == (rows, S) and r.n_nan_windows == want['n_nan_windows'] == ref.n_nan_windows == 0, what
+    assert np.isfinite(ref.log_evidence) and r.log_evidence == ref.log_evidence, what      # bit for bit `exact_dwell`'s
+    devs = {'logev': abs(r.log_evidence - want['logev']), 'log_count': log_deviation(r.log_count, want['log_count'], what)}
+    with np.errstate(divide='ignore'):
+        devs['tail'] = abs(np.exp(r.log_tail) - np.exp(want['log_tail']))
+    for name, v in devs.items():
+        assert v < (TOL_TAIL if name == 'tail' else TOL_LOG), (what, name, v)
+    if k_max is None or k_max >= T - 1:
+        assert r.log_tail == -np.inf and abs(r.pmf().sum() - 1) < 2 * TOL_LOG, what
+    else:
+        assert not np.isnan(r.log_tail) and abs(r.pmf().sum() + np.exp(r.log_tail) - 1) < TOL_TAIL, what
+    return devs
+
+
+def hold_contact(c, want, ref, target, T, what):
+    """ a `DwellFirstContact` against the oracle's answer and `exact_dwell`'s evidence: {name: deviation}, the bars asserted """
+    assert c.target == target and c.log_first.shape == (T,) and c.n_nan_windows == want['n_nan_windows'] == ref.n_nan_windows == 0, what
+    assert c.log_evidence == ref.log_evidence, what
+    devs = {f"log_first{target}": log_deviation(c.log_first, want['log_first'], what),
+            f"log_never{target}": log_deviation(c.log_never, want['log_never'], what)}
+    for name, v in devs.items():
+        assert v < TOL_LOG, (what, name, v)
+    with np.errstate(divide='ignore'):
+        assert abs(np.exp(c.log_first).sum() + np.exp(c.log_never) - 1) < 2 * TOL_LOG, what     # (as the pmf: logs within TOL_LOG)
+    return devs
+
+
+@pytest.mark.parametrize('item', DEC.WIDE_CASES, ids=DEC.wide_id)
+def test_against_oracle_wide(item):
+    """ four states, T > 256, non-geometric tables and the hard priors (tests/README_dwell_events.md, "The wide cases") """
+    case, k_max = item
+    S, T = case[:2]
+    model, x, prior, _, _ = DC.oracle_case(case)
+    want = DEC.wide_counts(case, k_max)
+    ref = bild_amd.exact_dwell(x, model, prior, marginals=False)
+    r = bild_amd.exact_dwell_switch_counts(x, model, prior, k_max=k_max)
+    devs = hold_counts(r, want, ref, S, T, k_max, item)
+    seconds = DEC.ORACLE_SECONDS[case, 'counts', k_max]
+    for target in DEC.WIDE_TARGETS[S] if k_max is None else ():
+        c = bild_amd.exact_dwell_first_contact(x, model, prior, target)
+        devs.update(hold_contact(c, DEC.wide_contact(case, target), ref, target, T, (item, target)))
+        seconds = max(seconds, DEC.ORACLE_SECONDS[case, target])
+    print(f"{DEC.wide_id(item)}: slowest oracle answer {seconds:.2f} s; " + ', '.join(f"{k} {v:.1e}" for k, v in devs.items()))
+    assert seconds < 20
+    if S == 1:
+        assert np.all(r.log_count[1:] == -np.inf) and abs(np.log(r.pmf()[0])) < TOL_LOG
+
+
 def test_identities_at_T1000():
     T = 1000
     rng = np.random.default_rng(31)
@@ -154,6 +205,65 @@ def test_bit_identity():
     complete, cut = calls['counts'](xs), calls['counts'](xs, k_max=5)
     for a, b in zip(complete, cut):
         assert b.log_count.shape == (6, 2) and np.array_equal(a.log_count[:6], b.log_count) and np.isfinite(b.log_tail)
+
+
+def test_ragged_batch_against_oracle():
+    """
+    `dwell_cases.ragged_case` in one call: four states, non-geometric tables, T = 1 ... 257, so that five of the six have ld, slot
+    and p.ntile that are not their own.  Each trajectory alone is held to its own oracle answer, and the batch is the
+    trajectories alone bit for bit, whole and with one trajectory a chunk.  Six trajectories are two workgroups of
+    dwell_contact_kernel, the second with two waves.
+    """
+    model, prior, xs, _ = DC.ragged_case()
+    S, Tm = 4, max(len(x) for x in xs)
+    refs = bild_amd.exact_dwell(xs, model, prior, marginals=False)
+    calls = {'counts': lambda trajs, **kw: bild_amd.exact_dwell_switch_counts(trajs, model, prior, **kw)}
+    for target in DEC.RAGGED_TARGETS:
+        calls[target] = lambda trajs, target=target, **kw: bild_amd.exact_dwell_first_contact(trajs, model, prior, target, **kw)
+    worst, seconds = {}, 0.0
+    for key, call in calls.items():
+        kind = 'counts' if key == 'counts' else 'contact'
+        batch = call(xs)
+        assert len(batch) == len(xs)
+        for j, (x, r, ref) in enumerate(zip(xs, batch, refs)):
+            T = len(x)
+            alone = call(x)
+            if kind == 'counts':
+                devs = hold_counts(alone, DEC.ragged_counts(j), ref, S, T, None, ('ragged', j))
+                seconds = max(seconds, DEC.ORACLE_SECONDS['ragged', j, 'counts'])
+                # alone, k_max is the trajectory's own T - 1: the levels it has are the batch's, the others -inf
+                assert r.log_count.shape == (Tm, S) and np.array_equal(alone.log_count, r.log_count[:T]) and np.all(r.log_count[T:] == -np.inf)
+                assert alone.log_evidence == r.log_evidence and alone.log_tail == r.log_tail == -np.inf and r.n_nan_windows == 0
+            else:
+                devs = hold_contact(alone, DEC.ragged_contact(j, key), ref, key, T, ('ragged', j, key))
+                seconds = max(seconds, DEC.ORACLE_SECONDS['ragged', j, key])
+                assert same(alone, r, kind), (j, key)
+            for name, v in devs.items():
+                worst[name] = max(worst.get(name, 0.0), v)
+        assert all(same(a, b, kind) for a, b in zip(batch, call(xs, scratch_bytes=1))), key
+    print(f"ragged: slowest oracle answer {seconds:.2f} s; " + ', '.join(f"{k} {v:.1e}" for k, v in worst.items()))
+    assert seconds < 20
+
+
+def test_first_contact_of_nine_trajectories():
+    """
+    nine trajectories in one call are three workgroups of dwell_contact_kernel (a wave per trajectory, four to a workgroup), the
+    last with a single wave: each equals itself alone bit for bit, in one chunk and with two trajectories a chunk
+    """
+    model, prior, xs = DEC.nine_trajectories()
+    assert len(xs) == 9
+    S, Tm = 4, max(len(x) for x in xs)
+    # a trajectory's share of a chunk (csrc/gauss_dwellevent.cpp), as `test_bit_identity` derives it: both forward tables, beta
+    # and gamma, and the row of first
+    slot = S * (Tm + 1)
+    forward = slot * 40 + 2 * 8 + 8 + Tm
+    per_traj = 2 * forward + 2 * slot * 8 + (Tm + 1) * 8
+    for target in DEC.RAGGED_TARGETS:
+        alone = [bild_amd.exact_dwell_first_contact(x, model, prior, target) for x in xs]
+        assert all(np.isfinite(a.log_evidence) and not np.any(np.isnan(a.log_first)) for a in alone)
+        for scratch in (0, 2 * per_traj + 8):
+            batch = bild_amd.exact_dwell_first_contact(xs, model, prior, target, scratch_bytes=scratch)
+            assert len(batch) == 9 and all(same(a, b, 'contact') for a, b in zip(alone, batch)), (target, scratch)
 
 
 def test_trajectory_without_a_profile():

@@ -12,6 +12,7 @@ from scipy.special import logsumexp
 
 import bild_amd
 import dwell_cases as DC
+import dwell_event_cases as DEC
 import dwell_occupancy_cases as DQC
 import segment_cases as C
 from bild_amd import _lib
@@ -80,6 +81,56 @@ def test_against_oracle_and_siblings(case):
               + ', '.join(f"{k} {v:.1e}" for k, v in {**devs, **sib}.items()))
         for name, v in {**devs, **sib}.items():
             assert v < TOL_LOG, (case, target, name, v)
+
+
+def hold_occupancy(r, want, ref, target, S, T, what):
+    """ a `DwellOccupancy` against the oracle's answer and `exact_dwell`'s evidence: {name: deviation}, the bars asserted """
+    assert r.target == target and r.log_occupancy.shape == (T + 1, S), what
+    assert r.n_nan_windows == want['n_nan_windows'] == ref.n_nan_windows == 0, what
+    assert np.isfinite(ref.log_evidence) and r.log_evidence == ref.log_evidence, what       # bit for bit `exact_dwell`'s
+    devs = {'logev': abs(r.log_evidence - want['logev']), 'log_occupancy': log_deviation(r.log_occupancy, want['log_occupancy'], what),
+            'sum pmf = 1': abs(logsumexp(log_pmf(r)))}
+    for name, v in devs.items():
+        assert v < TOL_LOG, (what, name, v)
+    return devs
+
+
+@pytest.mark.parametrize('item', DQC.WIDE_CASES, ids=DQC.wide_id)
+def test_against_oracle_wide(item):
+    """ four states, T > 256, non-geometric tables and the hard priors (tests/README_dwell_occupancy.md, "The wide cases") """
+    case, target = item
+    S, T = case[:2]
+    model, x, prior, _, _ = DC.oracle_case(case)
+    want = DQC.wide_answer(case, target)
+    ref = bild_amd.exact_dwell(x, model, prior, marginals=False)
+    r = bild_amd.exact_dwell_occupancy(x, model, prior, target)
+    devs = hold_occupancy(r, want, ref, target, S, T, item)
+    print(f"{DQC.wide_id(item)}: oracle {DQC.ORACLE_SECONDS[item]:.2f} s, {int(np.sum(r.pmf() > 1e-12))} bins above 1e-12, mean {r.mean():.2f}; "
+          + ', '.join(f"{k} {v:.1e}" for k, v in devs.items()))
+    assert DQC.ORACLE_SECONDS[item] < 20
+
+
+def test_ragged_batch_against_oracle():
+    """
+    `dwell_cases.ragged_case` in one call: four states, non-geometric tables, T = 1 ... 257, so that five of the six have ld, slot
+    and the stride of alpha that are not their own, and end before the chunk's last end frame.  Each trajectory of the batch is
+    held to its own oracle answer, and the batch is the trajectories alone bit for bit, whole and with one trajectory a chunk.
+    """
+    model, prior, xs, _ = DC.ragged_case()
+    refs = bild_amd.exact_dwell(xs, model, prior, marginals=False)
+    worst, seconds = {}, 0.0
+    for target in DEC.RAGGED_TARGETS:
+        batch = bild_amd.exact_dwell_occupancy(xs, model, prior, target)
+        assert len(batch) == len(xs)
+        for j, (x, r, ref) in enumerate(zip(xs, batch, refs)):
+            devs = hold_occupancy(r, DQC.ragged_answer(j, target), ref, target, 4, len(x), ('ragged', j, target))
+            seconds = max(seconds, DQC.ORACLE_SECONDS['ragged', j, target])
+            for name, v in devs.items():
+                worst[name] = max(worst.get(name, 0.0), v)
+            assert same(bild_amd.exact_dwell_occupancy(x, model, prior, target), r), (j, target)
+        assert all(same(a, b) for a, b in zip(batch, bild_amd.exact_dwell_occupancy(xs, model, prior, target, scratch_bytes=1))), target
+    print(f"ragged: slowest oracle answer {seconds:.2f} s; " + ', '.join(f"{k} {v:.1e}" for k, v in worst.items()))
+    assert seconds < 20
 
 
 def test_identities_at_T1000():

@@ -54,6 +54,55 @@ def test_against_oracle(case):
         assert v < TOL_LOG, (case, name, v)
 
 
+def hold_windows(r, want, ref, windows, what):
+    """ a `DwellWindowSupport` against the oracle's answer and `exact_dwell`'s evidence: {name: deviation}, the bars asserted """
+    assert r.windows.tolist() == [list(w[:2]) for w in windows] and r.targets == tuple(w[2] for w in windows), what
+    assert r.log_all.shape == (len(windows),) and r.n_nan_windows == want['n_nan_windows'] == ref.n_nan_windows == 0, what
+    assert np.isfinite(ref.log_evidence) and r.log_evidence == ref.log_evidence, what       # bit for bit `exact_dwell`'s
+    devs = {'logev': abs(r.log_evidence - want['logev']), 'log_all': log_deviation(r.log_all, want['log_all'], what)}
+    for name, v in devs.items():
+        assert v < TOL_LOG, (what, name, v)
+    return devs
+
+
+@pytest.mark.parametrize('item', DWC.WIDE_CASES, ids=DWC.wide_id)
+def test_against_oracle_wide(item):
+    """ four states, T > 256, non-geometric tables and the hard priors (tests/README_dwell_windows.md, "The wide cases") """
+    model, x, prior, _, _ = DC.oracle_case(item[0])
+    windows, want = DWC.wide_windows(item), DWC.wide_answer(item)
+    assert 0 < len(windows) <= DWC.MAX_WINDOWS
+    ref = bild_amd.exact_dwell(x, model, prior, marginals=False)
+    r = bild_amd.exact_dwell_windows(x, model, prior, windows)
+    devs = hold_windows(r, want, ref, windows, item)
+    fin = r.log_all[r.log_all > -np.inf]
+    print(f"{DWC.wide_id(item)}: oracle {DWC.ORACLE_SECONDS[item]:.2f} s, {len(windows)} windows, {len(windows) - len(fin)} at -inf, finite log_all "
+          f"from {np.min(fin, initial=0.0):.3g} to {np.max(fin, initial=-np.inf):.3g}; " + ', '.join(f"{k} {v:.1e}" for k, v in devs.items()))
+    assert DWC.ORACLE_SECONDS[item] < 20
+
+
+def test_ragged_batch_against_oracle():
+    """
+    `dwell_cases.ragged_case` in one call: four states, non-geometric tables, T = 1 ... 257, so that five of the six have ld, slot
+    and kappa offsets that are not their own.  Each trajectory of the batch is held to its own oracle answer on the spans that
+    fit it, and the batch is the trajectories alone bit for bit, whole and with one trajectory a chunk.
+    """
+    model, prior, xs, _ = DC.ragged_case()
+    ws = [DWC.ragged_windows(len(x)) for x in xs]
+    assert [len(w) for w in ws][0] == 2 and all(ws)
+    refs = bild_amd.exact_dwell(xs, model, prior, marginals=False)
+    batch = bild_amd.exact_dwell_windows(xs, model, prior, ws)
+    worst, seconds = {}, 0.0
+    for j, (x, w, r, ref) in enumerate(zip(xs, ws, batch, refs)):
+        devs = hold_windows(r, DWC.ragged_answer(j), ref, w, ('ragged', j))
+        seconds = max(seconds, DWC.ORACLE_SECONDS['ragged', j])
+        for name, v in devs.items():
+            worst[name] = max(worst.get(name, 0.0), v)
+        assert same(bild_amd.exact_dwell_windows(x, model, prior, w), r), j
+    assert all(same(a, b) for a, b in zip(batch, bild_amd.exact_dwell_windows(xs, model, prior, ws, scratch_bytes=1)))
+    print(f"ragged: slowest oracle answer {seconds:.2f} s, {sum(map(len, ws))} windows; " + ', '.join(f"{k} {v:.1e}" for k, v in worst.items()))
+    assert seconds < 20
+
+
 def sibling_deviations(x, model, prior, target, nan, frames):
     """ section 29's identities between the call and its siblings on the device, as deviations of logs, from ONE window call """
     S, T = model.msd.shape[0], len(x)
@@ -80,12 +129,21 @@ def sibling_deviations(x, model, prior, target, nan, frames):
     return devs
 
 
-@pytest.mark.parametrize('traj', [t for t in DWC.TRAJECTORIES if t[4] == 'omit' or t[2] != 'order0_gap'], ids=lambda t: DWC.case_id(t + (0,))[:-6])
+# the two wide cases of four states across seams, as (case,): every frame at T = 129, every 8th at T = 257
+WIDE_SIBLINGS = [((4, 129, (64, 100), 'markov'),), ((4, 257, (100,), 'nongeometric'),)]
+
+
+@pytest.mark.parametrize('traj', [t for t in DWC.TRAJECTORIES if t[4] == 'omit' or t[2] != 'order0_gap'] + WIDE_SIBLINGS,
+                         ids=lambda t: DWC.DEC.wide_id(t[0]) + '_wide' if len(t) == 1 else DWC.case_id(t + (0,))[:-6])
 def test_identities_against_the_siblings(traj):
-    S, T, _, _, nan = traj
-    model, x, prior, _, _ = DWC.oracle_case(*traj[:4])
+    if len(traj) == 1:
+        (S, T, _, _), nan = traj[0], 'propagate'
+        model, x, prior, _, _ = DC.oracle_case(traj[0])
+    else:
+        S, T, _, _, nan = traj
+        model, x, prior, _, _ = DWC.oracle_case(*traj[:4])
     for target in DWC.TARGETS[S]:
-        devs = sibling_deviations(x, model, prior, target, nan, list(range(T)))
+        devs = sibling_deviations(x, model, prior, target, nan, list(range(0, T, 8 if T > 256 else 1)))
         print(f"{target}: " + ', '.join(f"{k}: {v:.1e}" for k, v in devs.items()))
         assert all(v < TOL_LOG for v in devs.values()), (traj, target, devs)
 
