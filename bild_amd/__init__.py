@@ -25,6 +25,7 @@ from .exact import exact_dwell_lag, DwellLagResults  # noqa: F401
 from .exact import exact_dwell_switch_counts, DwellSwitchCounts, exact_dwell_first_contact, DwellFirstContact  # noqa: F401
 from .exact import exact_dwell_occupancy, DwellOccupancy, pooled_occupancy  # noqa: F401
 from .exact import exact_dwell_windows, DwellWindowSupport, DwellMapSupport  # noqa: F401
+from .exact import exact_dwell_visits, DwellVisits, pooled_visits  # noqa: F401
 from .amis import FixedkSampler, Dirichlet, CFC  # noqa: F401
 from .profiles import Loopingprofile  # noqa: F401
 from .trajectory import Trajectory  # noqa: F401

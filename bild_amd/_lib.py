@@ -207,6 +207,13 @@ _SIGNATURES_EXT = {
                                                 _ip, _ip, _ip, _ip, ctypes.c_uint, _vp]),
 }
 
+# the calls of include/bild_amd_visits.h: bound by `lib()` as the two tables above are, and no part of `exported_symbols()`
+_SIGNATURES_VISITS = {
+    # exact visit counts to a set of states under a dwell-time prior (gauss_dwellvis.cpp)
+    'bild_gauss_dwell_visits': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
+                                               ctypes.c_uint, ctypes.c_int64, _vp]),
+}
+
 _lib = None
 _torch_libdir = None     # set when the library was bound to the HIP runtime of an installed PyTorch
 _rccl_chosen = False
@@ -248,7 +255,7 @@ def lib():
                               f"or `make -C bild_amd/csrc` (there is no CPU fallback)")
         _share_hip_runtime_with_torch()
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_EXT}.items():
+        for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_EXT, **_SIGNATURES_VISITS}.items():
             fn = getattr(handle, name)
             fn.restype = restype
             fn.argtypes = argtypes
@@ -1534,6 +1541,24 @@ def gauss_dwell_occupancy(model, ts, log_init, log_jump, log_dwell, log_surv, ta
         'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_occ': np.empty((n, T_max + 1, S))}
     return _dwell_call('bild_gauss_dwell_occupancy', DwellOccupancyOut, model, ts, (log_init, log_jump, log_dwell, log_surv), outputs,
                        scalars=(target,), omit=omit, scratch_bytes=scratch_bytes)
+
+
+class DwellVisitsOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ('logev', 'n_nan_windows', 'log_visits', 'log_tail')]
+
+
+def gauss_dwell_visits(model, ts, log_init, log_jump, log_dwell, log_surv, target, n_max, omit=False, scratch_bytes=0):
+    """
+    exact posterior of the number of visits to a set of states under a dwell-time prior for every trajectory of the set
+    (bild_gauss_dwell_visits, include/bild_amd_visits.h), target the bit mask of the states of the set: a dict of logev,
+    log_tail (n_traj,), n_nan_windows (n_traj,) int64 and log_visits (n_traj, n_max + 1, S), -inf behind a trajectory's
+    (T + 1) // 2
+    """
+    outputs = lambda n, S, T_max: {
+        'logev': np.empty(n), 'n_nan_windows': np.empty(n, dtype=np.int64), 'log_visits': np.empty((n, max(int(n_max), -1) + 1, S)),
+        'log_tail': np.empty(n)}        # (a negative n_max: no row, and the call refuses it)
+    return _dwell_call('bild_gauss_dwell_visits', DwellVisitsOut, model, ts, (log_init, log_jump, log_dwell, log_surv), outputs,
+                       scalars=(n_max, target), omit=omit, scratch_bytes=scratch_bytes)
 
 
 class DwellWindowsOut(ctypes.Structure):

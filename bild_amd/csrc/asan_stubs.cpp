@@ -142,6 +142,10 @@ int launch_dwell_occupancy(const DwellParams &, const DwellOccupancy &, int, voi
 namespace bild {
 int launch_dwell_windows(const DwellParams &, const DwellWindows &, void *) { return 1; }
 }
+#include "gauss_dwellvis.h"
+namespace bild {
+int launch_dwell_visits(const DwellParams &, const DwellVisits &, int, void *) { return 1; }
+}
 #include "gauss_dwelldraw.h"
 namespace bild {
 int launch_dwelldraw_head(const DwelldrawParams &, void *) { return 1; }

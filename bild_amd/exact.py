@@ -46,6 +46,9 @@ frames spent in a set of states, the looped fraction of the trajectory; `pooled_
 `exact_dwell_windows` (bild_gauss_dwell_windows) is the exact posterior probability that every frame of a
 window is in a set of states, for any number of windows a trajectory; `ExactDwellResults.map_support` asks it about the MAP
 profile: how well the posterior supports each called segment and the placement of each called switch.
+
+`exact_dwell_visits` (bild_gauss_dwell_visits) is the exact posterior of the number of visits to a set of
+states: contact episodes, maximal runs of frames in the set, for any number of states; `pooled_visits` is that of a data set.
 """
 import math
 import warnings
@@ -1090,6 +1093,18 @@ class ExactDwellDraws:
         wanted = [target] if isinstance(target, (int, np.integer)) else list(target)
         return np.isin(self._states[:, :self.T], np.asarray(wanted, dtype=np.int64)).sum(axis=1).astype(np.int64)
 
+    def visits(self, target):
+        """
+        (n,) int array: the number of visits of each draw to ``target`` or, for a collection, to the set of its states: the
+        maximal runs of consecutive frames in the set, a run at frame 0 and a run that reaches frame T - 1 included (host only).
+        The histogram counterpart of `exact_dwell_visits`.
+        """
+        wanted = [target] if isinstance(target, (int, np.integer)) else list(target)
+        hit = np.isin(self._states[:, :self.T], np.asarray(wanted, dtype=np.int64))
+        if hit.shape[1] == 0:
+            return np.zeros(len(hit), dtype=np.int64)
+        return (hit[:, 0].astype(np.int64) + (hit[:, 1:] & ~hit[:, :-1]).sum(axis=1)).astype(np.int64)
+
     def all_in(self, u, v, target):
         """
         the fraction of the draws with every frame of [u, v), 0 <= u < v <= T, in ``target`` or, for a collection, in one of its
@@ -1645,6 +1660,122 @@ def pooled_occupancy(results):
         pmf = r.pmf()
         if np.any(np.isnan(pmf)):
             raise ValueError(f"result {j} is NaN (n_nan_windows = {r.n_nan_windows}, log_evidence = {r.log_evidence!r})")
+        total = np.convolve(total, pmf)
+    return total
+
+
+# ---------------------------------------------------------------- visits to a set of states (section 30)
+
+class DwellVisits(_Record):
+    """
+    `exact_dwell_visits` of one trajectory of T frames: the exact posterior of the number N of visits to a target set of states,
+    a visit being a maximal run of consecutive frames in the set.  A run at frame 0 counts, a run cut off by the end of the
+    trajectory counts, and a jump between two states of the set continues the visit: 0 <= N <= (T + 1) // 2.
+
+    traj, model, prior, nan : as given
+    target : the states of the set, a sorted tuple
+    log_evidence, n_nan_windows : `exact_dwell`'s numbers, bit for bit
+    log_visits : (n_max + 1, S) log P(N = n, theta_{T-1} = s | data) at [n, s], n_max at most (T + 1) // 2; -inf where the
+        probability is 0
+    log_tail : log P(N > n_max | data), computed as log(max(0, 1 - sum exp `log_visits`)): a difference from 1, accurate to about
+        1e-15 of the probability and no better; -inf exactly when n_max >= (T + 1) // 2
+
+    Normalised by `log_evidence`, not by its sum: that it adds up to 1 holds to rounding.  Under nan='propagate' a trajectory
+    with `n_nan_windows` > 0 is NaN in all but `n_nan_windows`; a trajectory without a profile of positive weight has
+    `log_evidence` -inf and NaN elsewhere.
+    """
+
+    __slots__ = ('traj', 'model', 'prior', 'nan', 'target', 'log_evidence', 'n_nan_windows', 'log_visits', 'log_tail')
+
+    def __repr__(self):
+        return (f"DwellVisits(T={len(self.traj)}, n_max={len(self.log_visits) - 1}, target={self.target}, "
+                f"log_evidence={self.log_evidence!r}, n_nan_windows={self.n_nan_windows})")
+
+    def pmf(self):
+        """ (n_max + 1,) P(N = n | data): the last states summed in ascending order.  It sums to 1 - exp(`log_tail`). """
+        return np.exp(self.log_visits).sum(axis=1)
+
+    def cdf(self):
+        """ (n_max + 1,) P(N <= n | data), the running sum of `pmf` """
+        return np.cumsum(self.pmf())
+
+    def mean(self):
+        """ sum_n n P(N = n | data): the posterior mean of N when `log_tail` is -inf, a lower bound otherwise """
+        return float(np.arange(len(self.log_visits)) @ self.pmf())
+
+    def var(self):
+        """ the posterior variance of N about `mean`, over the rows of the table (the whole of it when `log_tail` is -inf) """
+        pmf, n = self.pmf(), np.arange(len(self.log_visits))
+        return float((n - n @ pmf) ** 2 @ pmf)
+
+    def interval(self, level=0.95):
+        """
+        the central interval (lo, hi) in visits: lo the smallest n whose cdf reaches (1 - level) / 2, hi the smallest whose cdf
+        reaches 1 - (1 - level) / 2 (n_max where rounding keeps the cdf below it).  ValueError where `log_tail` leaves more
+        than (1 - level) / 2 outside the table: hi is then beyond n_max.
+        """
+        if not 0 < level < 1:
+            raise ValueError(f"level = {level!r}: a probability strictly between 0 and 1")
+        cdf = self.cdf()
+        if np.any(np.isnan(cdf)) or np.isnan(self.log_tail):
+            raise ValueError("the result is NaN: no interval")
+        tail = (1 - level) / 2
+        if math.exp(self.log_tail) > tail:
+            raise ValueError(f"P(N > n_max = {len(cdf) - 1}) = {math.exp(self.log_tail):.3g} exceeds (1 - level) / 2 = {tail:.3g}: "
+                             f"the upper end lies beyond the table, raise n_max")
+        lo, hi = (min(int(np.searchsorted(cdf, q, side='left')), len(cdf) - 1) for q in (tail, 1 - tail))
+        return lo, hi
+
+
+def exact_dwell_visits(trajs, model, prior, target, n_max=None, nan='propagate', scratch_bytes=0):
+    """
+    The exact posterior distribution of the number of visits of a `GenericGaussianModel` profile to the states `target` under a
+    dwell-time prior, jointly with the last state: the number of contact episodes, maximal runs of consecutive frames in the
+    set, for any number of states.  With one state as the target it is the number of that state's segments.  The forward
+    recursion of `exact_dwell` resolved by the number of visits begun, one device launch per end frame
+    (bild_gauss_dwell_visits).  No draws, no histogram noise in P(N = 0) and in the tail.
+
+    trajs, model, prior, nan, scratch_bytes : as for `exact_dwell`; a list gives a list of results from ONE device call.  A
+        trajectory of a chunk costs S T (n_max + 1) doubles of the longest T beside `exact_dwell`'s forward tables
+    target : a state or a collection of states, a non-empty proper subset of the model's (so a model of one state is refused)
+    n_max : the rows 0 ... n_max are computed; None: (T + 1) // 2 of the longest trajectory, the complete distribution.  Each
+        result holds the rows up to its own (T + 1) // 2 at most.
+
+    Every refusal is `exact_dwell`'s, the target's or a `n_max` that is no non-negative integer (ValueError) and is raised
+    before the trajectories are uploaded.  Returns `DwellVisits` or a list of them.
+    """
+    single, items = _check_exact_dwell(trajs, model, prior, nan)
+    states = _target_states(target, model.msd.shape[0])
+    if n_max is None:
+        n_max = (max([len(t) for t in items] + [0]) + 1) // 2
+    if isinstance(n_max, bool) or not isinstance(n_max, (int, np.integer)) or n_max < 0:
+        raise ValueError(f"n_max = {n_max!r}: a non-negative integer, or None for the complete distribution")
+    fields = lambda res, j, T: dict(target=states, n_nan_windows=int(res['n_nan_windows'][j]),
+                                    log_visits=res['log_visits'][j, :min(int(n_max), (T + 1) // 2) + 1].copy(),
+                                    log_tail=float(res['log_tail'][j]))
+    return _dwell_per_trajectory(_lib.gauss_dwell_visits, DwellVisits, single, items, model, prior, nan, fields,
+                                 sum(1 << s for s in states), int(n_max), scratch_bytes=scratch_bytes)
+
+
+def pooled_visits(results):
+    """
+    (sum_j n_max_j + 1,) the pmf of the total number of visits to the target set over several trajectories' `DwellVisits`:
+    given model and prior their posteriors are independent, so it is the convolution of their pmfs, in linear space and in the
+    order of the list (host only).  Refused (ValueError): an empty list, differing targets, a result that is NaN, a result
+    whose `log_tail` is not -inf (its table is cut: the total would miss mass at every count).
+    """
+    results = list(results)
+    if not results:
+        raise ValueError("no result to pool")
+    if any(r.target != results[0].target for r in results):
+        raise ValueError(f"the results have differing targets: {sorted(set(r.target for r in results))}")
+    total = np.ones(1)
+    for j, r in enumerate(results):
+        pmf = r.pmf()
+        if np.any(np.isnan(pmf)) or np.isnan(r.log_tail):
+            raise ValueError(f"result {j} is NaN (n_nan_windows = {r.n_nan_windows}, log_evidence = {r.log_evidence!r})")
+        if r.log_tail != -np.inf:
+            raise ValueError(f"result {j} is cut at n_max = {len(pmf) - 1} (log_tail = {r.log_tail!r}): pool complete distributions")
         total = np.convolve(total, pmf)
     return total
 
